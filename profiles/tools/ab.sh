@@ -12,7 +12,7 @@ EXTRA=${AB_BENCH_ARGS:-}
 for r in $(seq 1 "$ROUNDS"); do
     for v in "$@"; do
         name=$(basename "$v" .so)
-        timeout 300 python3 bench.py --library "$ROOT/$v" --no-cpu-baseline --no-extra-legs --steps "$STEPS" --warmup 5 $EXTRA > "$OUT/${name}_$r.json" 2> "$OUT/${name}_$r.err" || tail -3 "$OUT/${name}_$r.err"
+        timeout 300 python3 bench.py --full --library "$ROOT/$v" --no-cpu-baseline --no-extra-legs --steps "$STEPS" --warmup 5 $EXTRA > "$OUT/${name}_$r.json" 2> "$OUT/${name}_$r.err" || tail -3 "$OUT/${name}_$r.err"
     done
 done
 python3 - "$OUT" "$ROUNDS" "$@" <<'PY'

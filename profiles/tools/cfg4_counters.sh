@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/cfg4_counters
 mkdir -p "$OUT"; export TMPDIR=/tmp
 cd /tmp
-timeout 600 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT --kernel-trace --output-format csv -d "$OUT/pmc" -o run -- python3 $ROOT/bench.py --workload cfg4 --steps 3 --warmup 1 --no-cpu-baseline > /dev/null 2> "$OUT/pmc.err"
+timeout 600 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT --kernel-trace --output-format csv -d "$OUT/pmc" -o run -- python3 $ROOT/bench.py --full --workload cfg4 --steps 3 --warmup 1 --no-cpu-baseline > /dev/null 2> "$OUT/pmc.err"
 timeout 600 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT --kernel-trace --output-format csv -d "$OUT/pmc_stream" -o run -- python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extra-legs > /dev/null 2> "$OUT/pmc_stream.err"
 python3 - "$OUT" <<'PY'
 import csv, glob, sys, collections

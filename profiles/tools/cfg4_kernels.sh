@@ -6,7 +6,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"; export TMPDIR=/tmp
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run -- python3 $ROOT/bench.py --workload cfg4 --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/stats.err"
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run -- python3 $ROOT/bench.py --full --workload cfg4 --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/stats.err"
 python3 - "$OUT" <<'PY'
 import csv, glob, sys
 for f in glob.glob(sys.argv[1] + "/stats/**/*kernel_stats.csv", recursive=True):

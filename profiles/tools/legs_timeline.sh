@@ -1,12 +1,12 @@
 #!/bin/bash
-# GPU box: the last commands of the default bench line's run -- its extra legs (cfg4, mid_items, header_items, host_abi) -- in the
+# GPU box: the last commands of the --full bench line's run -- its extra legs (cfg4, mid_items, header_items, host_abi) -- in the
 # order they ran, with gaps and queues: what those legs' steps are made of.
 set -u
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/legs_timeline
 mkdir -p "$OUT"; export TMPDIR=/tmp
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --output-format csv -d "$OUT/trace" -o run -- python3 $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/err.txt"
+timeout 600 rocprofv3 --kernel-trace --output-format csv -d "$OUT/trace" -o run -- python3 $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/err.txt"
 python3 - "$OUT" <<'PY'
 import csv, glob, re, sys
 rows = []

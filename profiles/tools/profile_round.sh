@@ -16,10 +16,10 @@ if [ "${2:-}" != "skip-tests" ]; then
     timeout 1200 python3 -m pytest tests -m gpu -x -q > "$OUT/gpu_tests.log" 2>&1
     tail -2 "$OUT/gpu_tests.log"
 fi
-timeout 600 python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout 600 python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 tail -c 600 "$OUT/bench.json"
-timeout 600 python3 bench.py --workload cfg4 --no-cpu-baseline > "$OUT/bench_cfg4.json" 2> "$OUT/bench_cfg4.err"
-timeout 600 python3 bench.py --workload host-abi --no-cpu-baseline > "$OUT/bench_host_abi.json" 2> "$OUT/bench_host_abi.err"
+timeout 600 python3 bench.py --full --workload cfg4 --no-cpu-baseline > "$OUT/bench_cfg4.json" 2> "$OUT/bench_cfg4.err"
+timeout 600 python3 bench.py --full --workload host-abi --no-cpu-baseline > "$OUT/bench_host_abi.json" 2> "$OUT/bench_host_abi.err"
 tail -c 300 "$OUT/bench_cfg4.json"; tail -c 300 "$OUT/bench_host_abi.json"
 BENCH="python3 $ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra-legs"
 cd /tmp

@@ -36,13 +36,14 @@ def emulator():
     return EMU_SO
 
 
-def run_bench(emulator, nproc, extra=(), launcher=True):
+def run_bench(emulator, nproc, extra=(), launcher=True, full=True):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1")
     for name in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(name, None)
     bench = os.path.join(harness.REPO, "bench.py")
+    # (--full: the digests and the extra legs these tests check are not in a plain run)
     args = ["--gpus", str(nproc), "--steps", "2", "--warmup", "1", "--bytes", str(STREAM_BYTES),
-            "--no-cpu-baseline", "--library", emulator, *extra]
+            "--no-cpu-baseline", "--library", emulator, *(["--full"] if full else []), *extra]
     if nproc == 1 or not launcher:
         cmd = [sys.executable, bench, *args]  # (N > 1 without a launcher: bench.py starts its ranks itself)
     else:
@@ -129,7 +130,7 @@ def test_two_ranks_split_the_batch(emulator, oracle):
 
 
 def test_single_rank_line(emulator, oracle):
-    """The default line of one GPU: the stream, verified after the timed steps, with BASELINE configs[3] and the
+    """The --full line of one GPU: the stream, verified after the timed steps, with BASELINE configs[3] and the
     reference's entry points on host memory riding along as extra keys (here with a small batch)."""
     out = run_bench(emulator, 1, extra=("--buffers", "12", "--buffer-bytes", "16384", "--header-items", "3000"))
     check_line(out, 1)
@@ -144,3 +145,41 @@ def test_single_rank_line(emulator, oracle):
     assert out["header_items"]["bit_exact"] is True and out["header_items"]["items_per_s"] > 0 and "3000 items" in out["header_items"]["workload"]
     # what making the batch's plans cost rides along, and a traffic figure only where it was measured for the workload
     assert set(out["cfg4"]["plan_ms"]) == {"encode", "encode_resume", "decode"} and out["cfg4"]["roofline"]["traffic"] is None
+
+
+def test_plain_line_dumps_the_last_step(emulator, oracle, tmp_path):
+    """A plain run (no --full) is the headline alone: no digests, legs or CPU baseline.  --dump-outputs writes what the
+    last timed step computed -- the encoded stream and the decoded bytes as float32, the records as float64 -- and
+    those are the oracle's bytes."""
+    out = run_bench(emulator, 1, extra=("--dump-outputs", str(tmp_path)), full=False)
+    check_line(out, 1)
+    assert out["cpu_baseline"] is None and "sha256_encoded" not in out["config"] and "bit_exact" not in out["config"]
+    assert not {"cfg4", "mid_items", "header_items", "host_abi"} & set(out)
+    data = harness.splitmix64_bytes(5, STREAM_BYTES)
+    enc = oracle.encode_all(oracle.lib.oracle_table_coder_new(*harness.load_table()), data)
+    got = {f.stem: np.load(f) for f in tmp_path.glob("*.npy")}
+    assert set(got) == {"encoded", "encoded_index", "decoded", "decoded_index", "encode_records", "decode_records"}
+    assert sum(f.stat().st_size for f in tmp_path.glob("*.npy")) <= 64 << 20
+    assert got["encoded"].dtype == np.float32 and got["encode_records"].dtype == np.float64
+    assert np.array_equal(got["encoded_index"], np.arange(enc.size)) and np.array_equal(got["encoded"], enc.astype(np.float32))
+    assert np.array_equal(got["decoded_index"], np.arange(data.size)) and np.array_equal(got["decoded"], data.astype(np.float32))
+    assert got["encode_records"][0][:4].tolist() == [0, 0, STREAM_BYTES, enc.size]
+    assert got["decode_records"][0][[0, 2]].tolist() == [0, STREAM_BYTES]
+
+
+def test_two_ranks_dump_the_batch(emulator, oracle, tmp_path):
+    """--dump-outputs on configs[3] over two ranks: each rank's encoded streams laid end to end, its decoded buffers,
+    rank 1's files prefixed rank1_."""
+    buffers, size = 10, 16384
+    run_bench(emulator, 2, extra=("--workload", "cfg4", "--buffers", str(buffers), "--buffer-bytes", str(size),
+                                  "--dump-outputs", str(tmp_path)), full=False)
+    coder = oracle.lib.oracle_table_coder_new(*harness.load_table())
+    for rank, prefix in ((0, ""), (1, "rank1_")):
+        mine = range(rank, buffers, 2)
+        data = np.concatenate([harness.splitmix64_bytes(2 + i, size) for i in mine])
+        enc = np.concatenate([oracle.encode_all(coder, harness.splitmix64_bytes(2 + i, size)) for i in mine])
+        idx = np.load(tmp_path / (prefix + "encoded_index.npy")).astype(np.int64)
+        assert np.array_equal(np.load(tmp_path / (prefix + "encoded.npy")), enc[idx].astype(np.float32)), rank
+        idx = np.load(tmp_path / (prefix + "decoded_index.npy")).astype(np.int64)
+        assert np.array_equal(np.load(tmp_path / (prefix + "decoded.npy")), data[idx].astype(np.float32)), rank
+        assert len(np.load(tmp_path / (prefix + "decode_records.npy"))) == len(mine)
