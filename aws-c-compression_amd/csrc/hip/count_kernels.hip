@@ -1,0 +1,136 @@
+/*
+ * Symbol counts of a byte range on the device (aws_huffman_amd_symbol_counts, huffman_amd_build.h): the step in front of
+ * a coder fitted to the data (csrc/host/coder_build.c makes the code lengths and the coder from the 256 counts).
+ *
+ * count_kernel, a persistent grid: every workgroup keeps one histogram in LDS and reads its share of the 16-byte aligned
+ * body in grid-stride order, four 16-byte loads a lane in flight; workgroup 0 also counts the head (the bytes in front
+ * of the first aligned address) and the tail (behind the last whole 16 bytes).  At the end -- and after every
+ * `flush_bytes` it has read, so that no 32-bit LDS counter can overflow -- a workgroup adds its 256 sums to the
+ * caller's u64 counts with agent-scope atomic adds (one per bin that is not zero) and clears its histogram.
+ *
+ * The histogram is 32 copies of the 256 bins, interleaved: bin b of copy c is word 32 b + c, and lane l adds to copy
+ * l mod 32.  A ds_add_u32 of a wave is served in two groups of 32 lanes, and a group's 32 addresses then lie in 32
+ * different banks ((a / 4) mod 32) whatever the bytes are: uniform bytes and one repeated byte cost the same LDS cycles
+ * (with one copy a wave, 32 lanes on one bin take turns; profiles/tools/micro/probe_counts.hip measures both layouts).
+ */
+#include "kernels_common.hpp"
+#include "launch_common.hpp"
+
+namespace {
+
+constexpr u32 kCountThreads = 512;
+constexpr u32 kCountCopies = 32;
+constexpr u32 kCountUnroll = 4;                               /* 16-byte loads a lane has in flight */
+constexpr u32 kCountLdsBytes = 256u * kCountCopies * 4u;      /* 32 KiB: four workgroups (32 waves) a CU */
+constexpr u64 kCountStepBytes = (u64)kCountThreads * 16u * kCountUnroll; /* what a workgroup reads a step: 32 KiB */
+
+__device__ __forceinline__ void count_word(u32 *copy, u32 w) {
+    atomicAdd(&copy[((w >> 0) & 0xFFu) * kCountCopies], 1u);
+    atomicAdd(&copy[((w >> 8) & 0xFFu) * kCountCopies], 1u);
+    atomicAdd(&copy[((w >> 16) & 0xFFu) * kCountCopies], 1u);
+    atomicAdd(&copy[(w >> 24) * kCountCopies], 1u);
+}
+
+/* thread t < 256: bin t's sum over the copies to the caller's count, and the bin cleared (rotated by t: the 256 lanes
+ * of a read touch 32 banks, not one) */
+__device__ __forceinline__ void count_flush(u32 *tab, u64 *counts) {
+    const u32 t = threadIdx.x;
+    if (t < 256) {
+        u32 *row = tab + t * kCountCopies;
+        u64 sum = 0;
+#pragma unroll 8
+        for (u32 c = 0; c < kCountCopies; ++c) {
+            const u32 k = (c + t) & (kCountCopies - 1);
+            sum += row[k];
+            row[k] = 0;
+        }
+        if (sum) {
+            __hip_atomic_fetch_add(&counts[t], sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+/* body: n_vec 16-byte vectors at a 16-byte aligned address; head / tail: the bytes around it (workgroup 0's);
+ * steps_per_flush: steps of kCountStepBytes a workgroup reads between two flushes (>= 1) */
+__global__ __launch_bounds__(kCountThreads) void count_kernel(
+    const u8 *head, u32 head_len, const uint4 *body, u64 n_vec, const u8 *tail, u32 tail_len, u64 *counts,
+    u64 steps_per_flush) {
+    u32 *tab = reinterpret_cast<u32 *>(dyn_lds);
+    const u32 t = threadIdx.x;
+    if (t < 256) {
+        uint4 *row = reinterpret_cast<uint4 *>(tab + t * kCountCopies);
+#pragma unroll
+        for (u32 i = 0; i < kCountCopies / 4; ++i) {
+            row[i] = uint4{0u, 0u, 0u, 0u};
+        }
+    }
+    __syncthreads();
+    u32 *copy = tab + (t & (kCountCopies - 1));
+    if (blockIdx.x == 0) {
+        if (t < head_len) {
+            atomicAdd(&copy[(u32)head[t] * kCountCopies], 1u);
+        }
+        if (t < tail_len) {
+            atomicAdd(&copy[(u32)tail[t] * kCountCopies], 1u);
+        }
+    }
+    const u64 stride = (u64)gridDim.x * kCountThreads * kCountUnroll;
+    u64 base = (u64)blockIdx.x * kCountThreads * kCountUnroll; /* the same in every lane: the barriers below are uniform */
+    u64 steps = 0;
+    while (base < n_vec) {
+        if (steps == steps_per_flush) {
+            __syncthreads();
+            count_flush(tab, counts);
+            __syncthreads();
+            steps = 0;
+        }
+        uint4 v[kCountUnroll];
+        bool ok[kCountUnroll];
+#pragma unroll
+        for (u32 u = 0; u < kCountUnroll; ++u) {
+            const u64 i = base + u * kCountThreads + t;
+            ok[u] = i < n_vec;
+            v[u] = ok[u] ? body[i] : uint4{0u, 0u, 0u, 0u};
+        }
+#pragma unroll
+        for (u32 u = 0; u < kCountUnroll; ++u) {
+            if (ok[u]) {
+                count_word(copy, v[u].x);
+                count_word(copy, v[u].y);
+                count_word(copy, v[u].z);
+                count_word(copy, v[u].w);
+            }
+        }
+        base += stride;
+        ++steps;
+    }
+    __syncthreads();
+    count_flush(tab, counts);
+}
+
+} /* namespace */
+
+extern "C" {
+
+int hufk_symbol_counts(const void *input, uint64_t length, uint64_t *counts, uint64_t flush_bytes, void *stream) {
+    if (length == 0) {
+        return 0;
+    }
+    const u8 *in = (const u8 *)input;
+    const u64 misalign = (u64)((uintptr_t)in & 15u);
+    const u64 head_len = misalign ? (16u - misalign < length ? 16u - misalign : length) : 0u;
+    const u64 n_vec = (length - head_len) / 16u;
+    const u64 tail_len = length - head_len - n_vec * 16u;
+    const u64 steps = (n_vec + (u64)kCountThreads * kCountUnroll - 1) / ((u64)kCountThreads * kCountUnroll);
+    const uint32_t grid = hufk_host::persistent_grid(
+        count_kernel, kCountThreads, kCountLdsBytes, (uint32_t)(steps < 0xFFFFFFFFull ? (steps ? steps : 1) : 0xFFFFFFFFull));
+    /* a counter of a copy sees at most the bytes its workgroup reads between two flushes: below 2^32 */
+    u64 per_flush = flush_bytes / kCountStepBytes;
+    per_flush = per_flush ? per_flush : 1;
+    hipLaunchKernelGGL(
+        count_kernel, dim3(grid), dim3(kCountThreads), kCountLdsBytes, (hipStream_t)stream, in, (u32)head_len,
+        reinterpret_cast<const uint4 *>(in + head_len), n_vec, in + head_len + n_vec * 16u, (u32)tail_len, counts, per_flush);
+    return (int)hipGetLastError();
+}
+
+} /* extern "C" */

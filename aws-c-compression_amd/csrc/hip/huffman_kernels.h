@@ -203,6 +203,9 @@ int hufk_encode_one_block(
     const struct hufd_tables *tables, const struct hufd_enc_item *item, uint32_t symbols, const void *d_in, void *d_out,
     struct hufd_enc_result *result, uint32_t length_only, void *stream);
 int hufk_fill_splitmix64(void *dst, uint64_t len, uint64_t seed, void *stream);
+/* counts[b] += the bytes of input[0 .. length) equal to b, u64 agent-scope atomic adds (count_kernels.hip); flush_bytes:
+ * what a workgroup reads at most between two flushes of its 32-bit LDS counts (rounded down to 32 KiB, at least that) */
+int hufk_symbol_counts(const void *input, uint64_t length, uint64_t *counts, uint64_t flush_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,8 @@
  */
 #include "engine.h"
 
+#include <aws/compression/huffman_amd_build.h>
+
 #include <stdlib.h>
 #include <string.h>
 
@@ -2500,6 +2502,39 @@ int aws_huffman_amd_device_fill_splitmix64(struct aws_huffman_amd_engine *eng, v
     int err = hufk_fill_splitmix64(dst, size, seed, eng->stream);
     if (!err) {
         err = hufs_stream_sync(eng->stream);
+    }
+    return err ? raise_hip(err) : AWS_OP_SUCCESS;
+}
+
+/* what a workgroup of the counting kernel reads at most between two flushes of its 32-bit LDS counts: the default keeps
+ * every counter below 2^32 with room to spare (tests make it small, to run the flushes inside a launch) */
+static uint64_t s_count_flush_bytes = 0;
+
+void aws_huffman_amd_testing_set_count_flush_bytes(uint64_t bytes) {
+    __atomic_store_n(&s_count_flush_bytes, bytes, __ATOMIC_RELAXED);
+}
+
+int aws_huffman_amd_symbol_counts(int device, const void *device_input, uint64_t length, uint64_t *device_counts, void *stream) {
+    if (hufs_device_count() <= 0) {
+        return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION); /* no GPU: there is no CPU path */
+    }
+    if (length && (!device_input || !device_counts)) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    if (device < 0 && hufs_get_device(&device)) {
+        return aws_raise_error(AWS_ERROR_UNKNOWN);
+    }
+    if (device >= hufs_device_count()) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    if (length == 0) {
+        return AWS_OP_SUCCESS;
+    }
+    ON_DEVICE(device);
+    int err = hufk_init(); /* the grid's size: the device's compute units */
+    if (!err) {
+        const uint64_t asked = __atomic_load_n(&s_count_flush_bytes, __ATOMIC_RELAXED);
+        err = hufk_symbol_counts(device_input, length, device_counts, asked ? asked : (1ull << 30), stream);
     }
     return err ? raise_hip(err) : AWS_OP_SUCCESS;
 }
