@@ -121,13 +121,49 @@ static void *device_upload(const void *host, size_t size, void *stream, int *err
  * callback (reference huffman.h:48) about every index with the bits below it all zero and all one: the same
  * answer, no longer than the bits looked at, is an entry; anything else depends on later bits and gets a
  * table of its own.  Every code of the encode table must then come back out of the tables.
+ *
+ * A linked table is made HUFD_DEEP_SUB_BITS wide and, when none of its entries is a link, narrowed to the
+ * bits its answers depend on: entries that repeat in runs of 2^k lose k index bits (the link carries the
+ * width).  Only answers are asked for, so a decode-only coder gets the same tables.  The levels stay where
+ * they were (bits 10, 18, 26), so a look-up takes as many steps as before the narrowing.
+ *
+ * Size, for a canonical code (aws_huffman_amd_table_coder_from_lengths: codes in order of length, so the codes
+ * of one length are one run of the code space, and room that is left lies behind the last code).  Call the
+ * runs of lengths 11 .. 32 and the room left "classes"; a class of length L ends on a multiple of 2^(32-L).
+ *   - A table whose span holds one class of length L is either all codes (narrowed to L - depth bits: one
+ *     entry per code) or all links with at least one code below each: at most one entry per code and level,
+ *     3 * 256 = 768 entries.
+ *   - A table whose span holds the end of a class of length L inside it lies at a depth below L.  There are
+ *     at most 22 such ends (L = 11 .. 32), each inside one table per level: 22 tables at depth 10, 14 at depth
+ *     18 (L >= 19), of at most 256 entries, and 6 at depth 26 (L >= 27) of 64: 9600 entries.
+ * With the root's 1024 that is 11 392 <= HUFD_DEEP_MAX_ENTRIES for every canonical code of 1 .. 256 symbols and
+ * lengths up to 32 (what the data gives is nearer 1024 plus a few hundred).  Other prefix codes
+ * (aws_huffman_amd_table_coder_new with patterns of the caller's own) can need more -- 256 codes of 32 bits
+ * under 256 different 10-bit prefixes need about 150 000 entries: those stay without decode
+ * (aws_huffman_amd_engine_can_decode() == false), as huffman_amd.h and INTEGRATION.md say.
  */
 struct deep_builder {
     struct aws_huffman_symbol_coder *coder;
-    uint32_t *tab;
+    uint32_t *tab; /* HUFD_DEEP_MAX_ENTRIES, and room for the one table that is not narrowed yet */
     uint32_t used;
     bool ok;
 };
+
+/* how many index bits the link-free table of 1 << width entries at tab can lose: the largest k < width with every run of
+ * 2^k entries the same */
+static uint32_t deep_table_spare_bits(const uint32_t *tab, uint32_t width) {
+    uint32_t k = 0;
+    while (k + 1 < width) {
+        const uint32_t half = 1u << k;
+        for (uint32_t i = 0; i < (1u << width); i += 2 * half) {
+            if (tab[i] != tab[i + half]) {
+                return k;
+            }
+        }
+        ++k;
+    }
+    return k;
+}
 
 static void deep_table_fill(struct deep_builder *b, uint32_t base, uint32_t prefix, uint32_t depth, uint32_t width) {
     const uint32_t low = 32 - depth - width; /* window bits below this table's index */
@@ -142,15 +178,27 @@ static void deep_table_fill(struct deep_builder *b, uint32_t base, uint32_t pref
         } else if (low == 0) {
             b->ok = false; /* an answer longer than the window */
         } else {
-            const uint32_t sub = low < HUFD_DEEP_SUB_BITS ? low : HUFD_DEEP_SUB_BITS;
-            if (b->used + (1u << sub) > HUFD_DEEP_MAX_ENTRIES) {
-                b->ok = false;
+            uint32_t sub = low < HUFD_DEEP_SUB_BITS ? low : HUFD_DEEP_SUB_BITS;
+            /* (a table is opened full-width and narrowed afterwards, so `used` may run up to 1 << HUFD_DEEP_SUB_BITS entries
+             * past the maximum here -- the room deep_table_build allocates on top -- and deep_table_build's check of the
+             * final size decides) */
+            if (b->used > HUFD_DEEP_MAX_ENTRIES) {
+                b->ok = false; /* more tables than the kernels keep in LDS */
                 return;
             }
             const uint32_t at = b->used;
             b->used += 1u << sub;
-            b->tab[base + w] = HUFD_DEEP_LINK | (sub << 16) | at;
             deep_table_fill(b, at, bits, depth + width, sub);
+            if (b->ok && b->used == at + (1u << sub)) {
+                /* no table below this one: its entries are answers, and it is the last one made */
+                const uint32_t spare = deep_table_spare_bits(b->tab + at, sub);
+                for (uint32_t i = 0; i < (1u << (sub - spare)); ++i) {
+                    b->tab[at + i] = b->tab[at + (i << spare)];
+                }
+                sub -= spare;
+                b->used = at + (1u << sub);
+            }
+            b->tab[base + w] = HUFD_DEEP_LINK | (sub << 16) | at;
         }
     }
 }
@@ -166,11 +214,13 @@ static uint32_t deep_table_lookup(const uint32_t *tab, uint32_t window) {
 }
 
 static int deep_table_build(struct aws_huffman_amd_engine *eng, struct aws_huffman_symbol_coder *coder) {
-    struct deep_builder b = {coder, malloc(HUFD_DEEP_MAX_ENTRIES * sizeof(uint32_t)), 1u << HUFD_DEEP_ROOT_BITS, true};
+    struct deep_builder b = {
+        coder, malloc((HUFD_DEEP_MAX_ENTRIES + (1u << HUFD_DEEP_SUB_BITS)) * sizeof(uint32_t)), 1u << HUFD_DEEP_ROOT_BITS, true};
     if (!b.tab) {
         return aws_raise_error(AWS_ERROR_OOM);
     }
     deep_table_fill(&b, 0, 0, 0, HUFD_DEEP_ROOT_BITS);
+    b.ok = b.ok && b.used <= HUFD_DEEP_MAX_ENTRIES;
     /* the longest and the shortest code the decoder knows (an encoder may know fewer, or none) */
     for (uint32_t i = 0; i < b.used && b.ok; ++i) {
         const uint32_t e = b.tab[i];

@@ -91,7 +91,12 @@ int aws_huffman_amd_engine_new(
 AWS_COMPRESSION_API
 void aws_huffman_amd_engine_destroy(struct aws_huffman_amd_engine *engine);
 
-/* Longest code of the staged coder, and whether the engine can decode. */
+/* Longest code of the staged coder, and whether the engine can decode.  can_decode is false for a coder without a decode
+ * callback, for a decode callback that is not table-shaped, and for a coder with codes of more than 12 bits whose linked
+ * decode tables would pass 16 384 entries (64 KiB of LDS).  No canonical code does -- every coder of
+ * aws_huffman_amd_table_coder_from_lengths decodes -- but a prefix code with patterns of the caller's own can: 256 codes of
+ * 32 bits under 256 different 10-bit prefixes.  Such an engine still encodes; its decode entry points raise
+ * AWS_ERROR_UNSUPPORTED_OPERATION with nothing consumed and nothing written. */
 AWS_COMPRESSION_API
 uint32_t aws_huffman_amd_engine_max_code_bits(const struct aws_huffman_amd_engine *engine);
 AWS_COMPRESSION_API

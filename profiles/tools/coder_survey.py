@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Encode / decode rate of ONE 128 MiB stream for the coder profiles of tests/parity_cases.py (code-length shapes other
-than the test coder's), symbols drawn to match the code lengths and uniformly: which roads they take and how fast."""
+than the test coder's), symbols drawn to match the code lengths and uniformly: which roads they take and how fast.
+
+  usage: coder_survey.py [--library path/to/build.so] [--only name,name,...]
+(another build of the library beside this one, as profiles/tools/ab.sh does for bench.py; only these profiles)"""
 import ctypes as C
 import os
 import sys
@@ -13,7 +16,10 @@ sys.path.insert(0, os.path.join(REPO, "tests"))
 import harness  # noqa: E402
 import parity_cases as pc  # noqa: E402
 
-lib = harness.load_product()
+args = sys.argv[1:]
+library = args[args.index("--library") + 1] if "--library" in args else None
+only = args[args.index("--only") + 1].split(",") if "--only" in args else list(pc.CODER_PROFILES)
+lib = harness.load_product(library)
 n = 128 << 20
 eng = None
 slowest_at = 0
@@ -34,7 +40,7 @@ def timed(launch, reps):
 
 
 rng = np.random.default_rng(3)
-for name, rows in pc.CODER_PROFILES.items():
+for name, rows in ((k, pc.CODER_PROFILES[k]) for k in only):
     lengths = [l for count, l in rows for _ in range(count)]
     patterns, lens = pc.canonical_code(lengths)
     coder = lib.aws_huffman_amd_table_coder_new((C.c_uint32 * 256)(*patterns), (C.c_uint8 * 256)(*lens))

@@ -12,13 +12,15 @@ import traceback
 
 REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(REPO, "tests"))
+import build_api as ba  # noqa: E402
+import coder_shapes as cs  # noqa: E402
 import harness  # noqa: E402
 import parity_cases as pc  # noqa: E402
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 240.0
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1000
 only = sys.argv[3] if len(sys.argv) > 3 else ""  # a substring: only the rounds whose names hold it
-lib = harness.load_product()
+lib = ba.bind(harness.load_product())
 assert lib.aws_huffman_amd_device_count() >= 1
 w = pc.World(harness.oracle_codec(), harness.Codec(lib, "aws_"))
 eng = harness.Engine(lib, w.pcoder)
@@ -69,6 +71,9 @@ rounds = [
     ("quiet_plans", lambda s: pc.quiet_plans(w, n=300_000 + 997 * (s % 50), seed=s, engine=eng) if s % 3 == 2 else None),
     ("encode_roads", lambda s: pc.encode_roads(w, sizes=(200_000 + 1021 * (s % 30), 16384, 40_000 + s % 999, 1_000_000 + 4099 * (s % 20)), seed=s)
      if s % 4 == 3 else None),
+    # the coder as the swept dimension: six shapes from the seed, three through the library's own build path
+    ("coder_shape_sweep", lambda s: pc.coder_shape_sweep(w, cs.random_shapes(lib, s, 6), enc_bytes=100_000 + 1031 * (s % 60), seed=s,
+                                                         min_per_class=0)),
 ]
 rounds = [r for r in rounds if only in r[0]]
 t0 = time.time()

@@ -142,8 +142,19 @@ def one_pass_rule(lengths):
 
 
 def chunked_decode_rule(lengths):
-    """HUFD_DEC_MAX_LUT_BITS: codes of at most 12 bits."""
+    """HUFD_DEC_MAX_LUT_BITS: codes of at most 12 bits decode through the 12-bit table -- by the chunk kernels, or, when
+    all codes have one length, by dec_fixed (decode_rule tells the two apart)."""
     return max(lengths) <= 12
+
+
+def decode_rule(lengths):
+    """Which decoder a coder of these lengths (0 = no code) gets: "linked" (a code of more than HUFD_DEC_MAX_LUT_BITS bits:
+    linked tables, an item a thread / a workgroup / blocks of dec_wide), "fixed" (all codes of one length: dec_fixed,
+    symbol k at bit k * length) or "chunked" (sync + scan + emit over chunks of 32 KiB)."""
+    coded = [l for l in lengths if l]
+    if max(coded) > 12:
+        return "linked"
+    return "fixed" if min(coded) == max(coded) else "chunked"
 
 
 def skewed_geometric_counts(n_symbols=256, ratio=0.7, scale=1 << 40):

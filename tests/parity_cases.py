@@ -545,6 +545,222 @@ def long_streams_of_other_coders(w, names=("len4to12", "len2to12"), n=22_000_000
         eng.close()
 
 
+# ----------------------------------------------------------------------------- scenario: the coder as the swept dimension
+WIDE_MIN_BYTES = 4 * 32768  # HUFD_WIDE_MIN_BYTES: in a plan of a few items, a linked-table item from here on is decoded in blocks
+
+
+def shape_data(rng, lengths, kind, enc_bytes):
+    """Symbols of a coder with these lengths (coded ones only) that encode to about enc_bytes: "matched" drawn by
+    2^-length, "uniform", "shortest" only the symbols with the shortest code."""
+    coded = np.array([s for s, l in enumerate(lengths) if l])
+    lens = np.array([lengths[s] for s in coded], dtype=np.float64)
+    if kind == "matched":
+        prob = 2.0 ** -lens
+        prob /= prob.sum()
+    elif kind == "uniform":
+        prob = np.full(coded.size, 1.0 / coded.size)
+    else:
+        prob = (lens == lens.min()).astype(np.float64)
+        prob /= prob.sum()
+    n = max(1, int(enc_bytes * 8 / float((prob * lens).sum())))
+    return coded[rng.choice(coded.size, size=n, p=prob)].astype(np.uint8)
+
+
+def one_coder_shape(w, name, lengths, enc_bytes, modes, engine_check, rng):
+    import coder_shapes as cs
+
+    lib = w.product.lib
+    roads = cs.expected_roads(lengths)
+    longest, shortest = max(lengths), min(l for l in lengths if l)
+    uncoded = [s for s, l in enumerate(lengths) if not l]
+    patterns, lens = canonical_code(lengths)
+    pat_arr, len_arr = (C.c_uint32 * 256)(*patterns), (C.c_uint8 * 256)(*lens)
+    oc = w.oracle.lib.oracle_table_coder_new(pat_arr, len_arr)
+    pcoder = lib.aws_huffman_amd_table_coder_new(pat_arr, len_arr)
+    assert oc and pcoder, name
+    eng = harness.Engine(lib, pcoder)
+    # ---- routing, from the lengths alone
+    assert lib.aws_huffman_amd_engine_can_decode(eng.h), "%s: a prefix code the engine cannot decode (can_decode false)" % name
+    if engine_check:
+        assert bool(lib.aws_huffman_amd_engine_encodes_in_one_pass(eng.h)) == roads["one_pass"], (name, roads)
+        assert lib.aws_huffman_amd_engine_max_code_bits(eng.h) == longest, (name, longest)
+
+    def decode_stats_as_expected(plan, items):
+        if not engine_check:
+            return
+        st = eng.decode_stats(plan)
+        if roads["decode"] == "fixed":
+            assert st["by_blocks"] > 0 and st["by_pieces"] == 0, (name, st)
+        elif roads["decode"] == "chunked":
+            assert st["by_pieces"] > 0 and st["by_blocks"] == 0, (name, st)
+        else:  # no chunks, no dec_fixed: by_blocks counts the items long enough for dec_wide_*, and nothing else
+            wide = sum(1 for it in items if it["in_len"] >= WIDE_MIN_BYTES)
+            assert st["by_pieces"] == 0 and st["pieces"] == 0 and st["by_blocks"] == wide, (name, st, wide)
+            assert st["by_workgroup"] + st["by_blocks"] > 0, (name, st)
+            assert st["by_thread"] + st["by_workgroup"] + st["by_blocks"] + st["empty"] == st["items"], (name, st)
+
+    encodings = {}
+    for kind in ("matched", "uniform", "shortest"):
+        data = shape_data(rng, lengths, kind, enc_bytes)
+        n = data.size
+        # ---- encode: one host-pointer call
+        want = w.oracle.encode_all(oc, data)
+        got = w.product.encode_all(pcoder, data)
+        assert np.array_equal(got, want), "%s: host-pointer encode of %s data differs" % (name, kind)
+        encodings[kind] = (data, want)
+        # ---- encode: a device plan of one long item
+        cap = want.size + 8
+        d_in, d_out = eng.alloc(n), eng.alloc(cap + 8)
+        eng.upload(d_in, data)
+        eng.fill(d_out, SENTINEL, cap + 8)
+        plan = eng.encode_plan([dict(in_offset=0, in_len=n, out_offset=3, out_capacity=cap, eos_padding=0xFF)])
+        eng.encode_launch(plan, d_in, d_out)
+        e = w.oracle.new_encoder(oc, eos_padding=0xFF)
+        dst = np.full(cap, SENTINEL, np.uint8)
+        r = w.oracle.encode_call(e, data, 0, dst, 0, cap)
+        assert eng.encode_results(plan, 1) == [(r.rc, r.err, r.consumed, r.produced, r.state[0], r.state[1])], (name, kind)
+        assert r.rc == 0 and r.produced == want.size
+        out = eng.download(d_out, cap + 8)
+        assert np.array_equal(out[3:3 + cap], dst) and np.all(out[:3] == SENTINEL) and np.all(out[3 + cap:] == SENTINEL), (name, kind)
+        if engine_check and n > 4096:  # (shorter: a thread's or a wave's item, whatever the coder)
+            assert eng.encode_road(plan) == (1 if roads["one_pass"] else 0), (name, kind, eng.encode_road(plan))
+        lib.aws_huffman_amd_encode_plan_destroy(plan)
+        eng.free(d_in)
+        eng.free(d_out)
+        # ---- decode: the stream whole, damaged, cut, short of room, entered inside a byte
+        enc = want
+        assert enc.size > 5
+        third, half = enc.size // 3, enc.size // 2
+        damaged, ones, zeros = enc.copy(), enc.copy(), enc.copy()
+        damaged[half:half + 4] ^= 0xA5
+        ones[third:third + 6] = 0xFF
+        zeros[third:third + 6] = 0x00
+        inside = enc[5:5 + 70000]
+        streams = [(enc, 0, n), (damaged, 0, n), (ones, 0, n), (zeros, 0, n), (enc[:third + 5], 0, n), (enc, 0, n // 2 + 3),
+                   (enc[:700], 0, 700 * 8 // shortest + 8), (enc[:40], 0, 40 * 8 // shortest + 8),
+                   (inside, 3, inside.size * 8 // shortest + 8)]
+        if kind == "matched":
+            noise = rng.integers(0, 256, 40000).astype(np.uint8)
+            streams.append((noise, 0, 40000 * 8 // shortest + 8))
+        decode_items_like_the_oracle(w, eng, oc, streams, rng, "%s, %s data" % (name, kind), modes=modes, kinds=2,
+                                     with_plan=decode_stats_as_expected)
+    # ---- decode: the reference ABI, the whole stream in pieces of 7001 bytes
+    data, enc = encodings["matched"]
+    n = data.size
+    ddo, ddp = w.oracle.new_decoder(oc), w.product.new_decoder(pcoder)
+    oo, op = np.full(n + 8, SENTINEL, np.uint8), np.full(n + 8, SENTINEL, np.uint8)
+    produced = 0
+    for off in range(0, enc.size, 7001):
+        r = paired_decode(w, ddo, ddp, enc, off, min(off + 7001, enc.size), oo, op, produced, n)
+        produced += r.produced
+    assert produced == n and np.array_equal(op[:n], data), name
+    # ---- encode: a batch of short items and of items either side of one tile and one segment
+    item_lens = [int(rng.integers(1, 601)) for _ in range(24)] + [4095, 4096, 4097, 16383, 16384, 16385]
+    blobs = []
+    for i, m in enumerate(item_lens):
+        kind_data = encodings[("matched", "uniform", "shortest")[i % 3]][0]
+        at = int(rng.integers(0, max(kind_data.size - m, 1)))
+        b = np.resize(kind_data[at:at + m], m).copy()
+        if uncoded and i % 4 == 1:  # a symbol without a code somewhere inside
+            b[int(rng.integers(0, m))] = uncoded[int(rng.integers(0, len(uncoded)))]
+        blobs.append(b)
+    in_offs, pos = [], 1
+    for b in blobs:
+        in_offs.append(pos)
+        pos += b.size + int(rng.integers(0, 3))
+    host_in = np.zeros(pos + 64, np.uint8)
+    for b, o in zip(blobs, in_offs):
+        host_in[o:o + b.size] = b
+    items, pos = [], 3
+    for i, (b, o) in enumerate(zip(blobs, in_offs)):
+        full = (longest * b.size + 7) // 8 + 2
+        cap = [full, full, int(rng.integers(0, full + 1)), full, 0][i % 5]
+        items.append(dict(in_offset=o, in_len=b.size, out_offset=pos, out_capacity=cap, eos_padding=[0xFF, 0x00, 0xA5][i % 3]))
+        pos += cap + int(rng.integers(1, 9))
+    out_total = pos + 64
+    d_in, d_out = eng.alloc(host_in.size), eng.alloc(out_total)
+    eng.upload(d_in, host_in)
+    eng.fill(d_out, SENTINEL, out_total)
+    plan = eng.encode_plan(items)
+    eng.encode_launch(plan, d_in, d_out)
+    res = eng.encode_results(plan, len(items))
+    want_out = np.full(out_total, SENTINEL, np.uint8)
+    for i, (b, it) in enumerate(zip(blobs, items)):
+        e = w.oracle.new_encoder(oc, eos_padding=it["eos_padding"])
+        c = it["out_capacity"]
+        dst = np.full(c + 1, SENTINEL, np.uint8)
+        r = w.oracle.encode_call(e, b, 0, dst, 0, c)
+        want_out[it["out_offset"]:it["out_offset"] + c] = dst[:c]
+        assert res[i] == (r.rc, r.err, r.consumed, r.produced, r.state[0], r.state[1]), (name, i, it, res[i], r)
+    assert np.array_equal(eng.download(d_out, out_total), want_out), "%s: batch encode: wrong bytes, or bytes outside an item" % name
+    lib.aws_huffman_amd_encode_plan_destroy(plan)
+    eng.free(d_in)
+    eng.free(d_out)
+    # ---- encode: symbols without a code inside a long input: the call stops where the oracle's stops
+    if uncoded:
+        data = encodings["matched"][0][:60000].copy()
+        spots = np.sort(rng.choice(data.size, size=min(5, data.size), replace=False))
+        data[spots] = rng.choice(uncoded, size=spots.size)
+        eo, ep = w.oracle.new_encoder(oc), w.product.new_encoder(pcoder)
+        cap = data.size * 4 + 64
+        do, dp = np.full(cap, SENTINEL, np.uint8), np.full(cap, SENTINEL, np.uint8)
+        r = paired_encode(w, eo, ep, data, 0, do, dp, 0, cap)
+        assert r.rc != 0 and r.err == UNKNOWN_SYMBOL and r.consumed <= int(spots[0]) + 1, (name, r, spots)
+    eng.close()
+    lib.aws_huffman_amd_table_coder_destroy(pcoder)
+    w.oracle.lib.oracle_table_coder_destroy(oc)
+
+
+def coder_shape_sweep(w, shapes, enc_bytes, modes=(None, "long-way", "tails-apart"), engine_check=True, seed=211, min_per_class=3):
+    """shapes: (name, 256 code lengths) each (tests/coder_shapes.py).  For every shape the oracle's and the product's table
+    coder of canonical_code(lengths) and one engine: the roads the engine reports against coder_shapes.expected_roads
+    (engine_check), streams of about enc_bytes ENCODED bytes of three kinds of data (a coder of 1-2-bit codes must fill
+    its chunks too) through the host-pointer calls, device plans of one long item and of a batch, with symbols without a
+    code where the shape has any, and the decode of every stream whole, damaged, overwritten with ones and zeros, cut,
+    short of room, of its first bytes, entered inside a byte, of arbitrary bytes, and in pieces through the reference
+    ABI: every record and byte as the oracle has them.  No shape is skipped; a shape whose engine cannot decode fails.
+    Returns how many shapes ran per road class: at least min_per_class of each (3 in the tests; a soak that draws a few
+    shapes per call asks for none)."""
+    import coder_shapes as cs
+
+    ran = dict.fromkeys(cs.ROAD_CLASSES, 0)
+    for k, (name, lengths) in enumerate(shapes):
+        size = enc_bytes if isinstance(enc_bytes, int) else enc_bytes[k]  # (one size, or one per shape)
+        one_coder_shape(w, name, lengths, size, modes, engine_check, np.random.default_rng([seed, k]))
+        for c in cs.road_classes(lengths):
+            ran[c] += 1
+    assert all(ran[c] >= min_per_class for c in cs.ROAD_CLASSES), ran
+    return ran
+
+
+def long_streams_of_swept_coders(w, names=("1,3,5,5,4x7,8x9+240x12", "256x12", "255x11+1x13", "fitted(1,16)"),
+                                 enc_bytes=20 << 20, seed=223):
+    """One stream of about 20 MiB encoded per shape of coder_shapes.BOUNDARY: past a scan run of 256 chunks (8 MiB) and the
+    dec_wide_* thresholds; whole, damaged, cut and short of room."""
+    import coder_shapes as cs
+
+    rng = np.random.default_rng(seed)
+    for name in names:
+        lengths = cs.BOUNDARY[name]
+        patterns, lens = canonical_code(lengths)
+        pat_arr, len_arr = (C.c_uint32 * 256)(*patterns), (C.c_uint8 * 256)(*lens)
+        oc = w.oracle.lib.oracle_table_coder_new(pat_arr, len_arr)
+        pcoder = w.product.lib.aws_huffman_amd_table_coder_new(pat_arr, len_arr)
+        assert oc and pcoder
+        data = shape_data(rng, lengths, "matched", enc_bytes)
+        n = data.size
+        enc = w.oracle.encode_all(oc, data)
+        damaged = enc.copy()
+        damaged[enc.size // 2 + 777:enc.size // 2 + 781] ^= 0xA5
+        eng = harness.Engine(w.product.lib, pcoder)
+        assert w.product.lib.aws_huffman_amd_engine_can_decode(eng.h), name
+        streams = [(enc, 0, n), (damaged, 0, n), (enc[: enc.size // 3 + 5], 0, n), (enc, 0, n // 2 + 3)]
+        decode_items_like_the_oracle(w, eng, oc, streams, rng, "long stream of %s" % name, kinds=2)
+        eng.close()
+        w.product.lib.aws_huffman_amd_table_coder_destroy(pcoder)
+        w.oracle.lib.oracle_table_coder_destroy(oc)
+
+
 # ----------------------------------------------------------------------------- scenario: items sharded over several engines (one per GPU)
 def sharded_items(w, devices=(0, 0, 0), n_items=23, seed=71, item_len=16384):
     """huffman_amd.h "several GPUs": item i runs on shard i mod G (the split of BASELINE configs[3]),
@@ -1511,9 +1727,10 @@ def tiny_decode_items(w, n_items=1500, seed=41, engine=None, profile=None, max_l
         eng.close()
 
 
-def decode_items_like_the_oracle(w, eng, ocoder, streams, rng, label, modes=(None,), kinds=3):
+def decode_items_like_the_oracle(w, eng, ocoder, streams, rng, label, modes=(None,), kinds=3, with_plan=None):
     """streams: (encoded bytes, first bit, output capacity) each; one plan of them all, launched twice per mode, every
-    record and every output byte (and the bytes between the outputs) as the oracle has them."""
+    record and every output byte (and the bytes between the outputs) as the oracle has them.  with_plan(plan, items):
+    called after the launches, before the plan goes (for assertions on aws_huffman_amd_decode_plan_stats)."""
     offs, pos = [], 3
     for e, _, _ in streams:
         offs.append(pos)
@@ -1552,6 +1769,8 @@ def decode_items_like_the_oracle(w, eng, ocoder, streams, rng, label, modes=(Non
                 for i, (it, (key, _)) in enumerate(zip(items, expect)):
                     assert res[i] == key, (label, mode, i, it, res[i], key)
                 assert np.array_equal(eng.download(d_sym, sym_total), want), (label, mode)
+    if with_plan is not None:
+        with_plan(plan, items)
     eng.lib.aws_huffman_amd_decode_plan_destroy(plan)
     eng.free(d_enc)
     eng.free(d_sym)

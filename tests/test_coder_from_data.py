@@ -10,6 +10,7 @@ import subprocess
 import pytest
 
 import build_api as ba
+import coder_shapes as cs
 import harness
 
 
@@ -197,6 +198,43 @@ def test_def_round_trip(lib):
     text = ba.to_def(lib, coder)
     back = lib.aws_huffman_amd_table_coder_from_def(text, len(text))
     assert ba.coder_rows(back) == ba.coder_rows(coder)
+
+
+@pytest.mark.parametrize("max_bits", [13, 15, 16, 20, 32])
+def test_swept_coders_def_round_trip(lib, max_bits):
+    """Every coder the build path makes of the random count families of tests/coder_shapes.py (half of them a few heavy
+    bytes, a flat tail and three rare bytes) at (1, max_bits): its .def text gives the same coder back."""
+    for name, lengths in cs.product_shapes(lib, 300 + max_bits, 40, max_bits=max_bits):
+        coder = lib.aws_huffman_amd_table_coder_from_lengths(ba.U8x256(*lengths))
+        assert coder, name
+        rows = ba.coder_rows(coder)
+        assert rows == ba.canonical_rows(lengths), name
+        text = ba.to_def(lib, coder)
+        back = lib.aws_huffman_amd_table_coder_from_def(text, len(text))
+        assert back and ba.coder_rows(back) == rows, name
+        decode_all(back, rows)
+        lib.aws_huffman_amd_table_coder_destroy(back)
+        lib.aws_huffman_amd_table_coder_destroy(coder)
+
+
+@pytest.mark.parametrize("max_bits", [13, 15, 16, 20, 32])
+def test_swept_coders_can_be_decoded(lib, max_bits):
+    """... and an engine of it decodes (the emulator library: an engine needs a device): whatever
+    aws_huffman_amd_table_coder_from_lengths returns, the linked decode tables hold."""
+    emu_dir = os.path.join(harness.REPO, "tests", "emu")
+    subprocess.check_call(["make", "-s", "-C", emu_dir], stdout=subprocess.DEVNULL)
+    emu = ba.bind(harness.load_product(os.path.join(emu_dir, "libaws-c-compression-emu.so")))
+    past_12 = 0
+    for name, lengths in cs.product_shapes(lib, 300 + max_bits, 40, max_bits=max_bits):
+        coder = emu.aws_huffman_amd_table_coder_from_lengths(ba.U8x256(*lengths))
+        assert coder, name
+        eng = harness.Engine(emu, coder)
+        assert emu.aws_huffman_amd_engine_can_decode(eng.h), (name, sorted(set(lengths)))
+        assert emu.aws_huffman_amd_engine_max_code_bits(eng.h) == max(lengths), name
+        past_12 += max(lengths) > 12
+        eng.close()
+        emu.aws_huffman_amd_table_coder_destroy(coder)
+    assert past_12 >= 10, past_12  # (the linked tables are what this is about)
 
 
 GENERATOR = os.path.join(harness.REPO, "oracle", "_ref", "huffman_generator")

@@ -11,6 +11,8 @@ import subprocess
 
 import pytest
 
+import build_api as ba
+import coder_shapes as cs
 import harness
 import parity_cases as pc
 
@@ -194,6 +196,52 @@ def test_first_bit_offsets(world):
 
 def test_other_coders(world):
     pc.other_coders(world, n=60000)
+
+
+def test_coder_shape_sweep(world):
+    """The coder as the swept dimension (tests/coder_shapes.py): every boundary shape at 140 000 encoded bytes (four
+    chunks and a bit), then shapes drawn from a seed at 40 000.  Budget: about a third of this module's time, nearly all of
+    it the boundary list; when that has to shrink, the random shapes go, never the boundary list."""
+    boundary, drawn = list(cs.BOUNDARY.items()), cs.random_shapes(ba.bind(world.product.lib), 5, 6)
+    print(pc.coder_shape_sweep(world, boundary + drawn, enc_bytes=[140_000] * len(boundary) + [40_000] * len(drawn)))
+
+
+def test_table_past_the_linked_tables_capacity(world):
+    """What huffman_amd.h and INTEGRATION.md say of a prefix code that is not canonical and whose linked decode tables
+    would pass HUFD_DEEP_MAX_ENTRIES -- 256 codes of 32 bits under 256 different 10-bit prefixes: the engine encodes (as
+    the oracle does), reports can_decode false, and every decode entry point raises AWS_ERROR_UNSUPPORTED_OPERATION
+    with nothing consumed and nothing written.  Never a wrong byte."""
+    import ctypes as C
+
+    import numpy as np
+
+    lib = world.product.lib
+    patterns = [((s << 22) | ((s * 2654435761) & 0x3FFFFF)) & 0xFFFFFFFF for s in range(256)]
+    pat_arr, len_arr = (C.c_uint32 * 256)(*patterns), (C.c_uint8 * 256)(*([32] * 256))
+    oc = world.oracle.lib.oracle_table_coder_new(pat_arr, len_arr)
+    pcoder = lib.aws_huffman_amd_table_coder_new(pat_arr, len_arr)
+    assert oc and pcoder
+    eng = harness.Engine(lib, pcoder)
+    assert not lib.aws_huffman_amd_engine_can_decode(eng.h)
+    assert lib.aws_huffman_amd_engine_max_code_bits(eng.h) == 32
+    data = np.random.default_rng(3).integers(0, 256, 20_000).astype(np.uint8)
+    want = world.oracle.encode_all(oc, data)
+    assert np.array_equal(world.product.encode_all(pcoder, data), want)
+    r, back = world.oracle.decode_all(oc, want, data.size)
+    assert r.rc == 0 and np.array_equal(back, data)  # (a stream the reference decodes)
+    dst = np.full(data.size + 8, pc.SENTINEL, np.uint8)
+    r = world.product.decode_call(world.product.new_decoder(pcoder), want, 0, want.size, dst, 0, data.size)
+    assert (r.rc, r.err, r.consumed, r.produced) == (-1, harness.AWS_ERROR_UNSUPPORTED_OPERATION, 0, 0), r
+    assert np.all(dst == pc.SENTINEL)
+    plan = C.c_void_p()
+    item = (harness.AmdDecodeItem * 1)()
+    item[0].in_len, item[0].out_capacity = want.size, data.size
+    lib.aws_reset_error()
+    assert lib.aws_huffman_amd_decode_plan_new(C.byref(plan), eng.h, item, 1) == -1
+    assert lib.aws_last_error() == harness.AWS_ERROR_UNSUPPORTED_OPERATION
+    eng.close()
+    lib.aws_huffman_amd_table_coder_destroy(pcoder)
+    world.oracle.lib.oracle_table_coder_destroy(oc)
 
 
 def test_dense_symbols(world):

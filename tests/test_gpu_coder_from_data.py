@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import build_api as ba
+import coder_shapes as cs
 import harness
 
 pytestmark = pytest.mark.gpu
@@ -157,8 +158,11 @@ def fitted_round_trip(lib, eng, oracle, data, lo, hi, flags, one_pass):
         (rc, err, dproduced, _), = fitted.decode_results(dplan, 1)
         assert rc == 0 and dproduced == n
         stats = fitted.decode_stats(dplan)
-        if len({l for l in lengths if l}) == 1:
+        if ba.decode_rule(lengths) == "fixed":
             assert stats["by_blocks"] > 0, stats  # codes of one length (uniform bytes: the flat 8-bit code): dec_fixed
+        elif ba.decode_rule(lengths) == "linked":
+            # a code past 12 bits: the item is a workgroup's, or (long enough) decoded in blocks across the chip; no chunks
+            assert stats["by_workgroup"] + stats["by_wave"] + stats["by_blocks"] > 0 and stats["by_pieces"] == 0, stats
         else:
             assert stats["by_pieces"] > 0, stats
         assert np.array_equal(fitted.download(d_back, n), data)
@@ -181,6 +185,20 @@ def test_fitted_coder_end_to_end(lib, eng, oracle, shape):
             "uniform": lambda: harness.splitmix64_bytes(23, n)}[shape]()
     lengths = fitted_round_trip(lib, eng, oracle, data, 4, 12, ba.CODE_EVERY_SYMBOL, True)
     assert ba.one_pass_rule(lengths) and ba.chunked_decode_rule(lengths)
+
+
+def test_heavy_bytes_and_a_flat_tail(lib, eng, oracle):
+    """A few heavy bytes, a flat tail and three rare bytes at (1, 16), only the bytes that occur coded: most of the codes
+    have 11-12 bits and a few more, under more ten-bit prefixes than 8-bit linked tables had room for.  The engine of
+    the library's own coder must decode what it encodes."""
+    counts = cs.heavy_flat_rare_counts(np.random.default_rng(45))
+    once = np.repeat(np.arange(256, dtype=np.uint8), counts.astype(np.int64))
+    data = np.tile(once, max(1, 32 * MiB // once.size))
+    np.random.default_rng(42).shuffle(data)
+    lengths = fitted_round_trip(lib, eng, oracle, data, 1, 16, 0, False)
+    assert ba.decode_rule(lengths) == "linked" and not ba.one_pass_rule(lengths), sorted(set(lengths))
+    prefixes = {p >> (l - 10) for p, l in ba.canonical_rows(lengths) if l > 10}
+    assert len(prefixes) > 60, len(prefixes)  # (more linked tables than fitted before they were narrowed)
 
 
 def test_no_lower_bound(lib, eng, oracle):

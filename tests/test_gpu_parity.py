@@ -10,6 +10,8 @@ import os
 import numpy as np
 import pytest
 
+import build_api as ba
+import coder_shapes as cs
 import harness
 import parity_cases as pc
 
@@ -208,6 +210,17 @@ def test_mid_sized_encode_items(world, engine):
 
 def test_long_streams_of_other_coders(world):
     pc.long_streams_of_other_coders(world)
+
+
+def test_coder_shape_sweep(world):
+    """The coder as the swept dimension (tests/coder_shapes.py): every boundary shape at about 1.2 MiB encoded -- several
+    chunks, more than one workgroup per kernel -- and 40 shapes drawn from a seed."""
+    boundary, drawn = list(cs.BOUNDARY.items()), cs.random_shapes(ba.bind(world.product.lib), 7, 40)
+    print(pc.coder_shape_sweep(world, boundary + drawn, enc_bytes=[1_250_000] * len(boundary) + [160_000] * len(drawn)))
+
+
+def test_long_streams_of_swept_coders(world):
+    pc.long_streams_of_swept_coders(world)
 
 
 def test_device_plans_of_other_coders(world):
