@@ -206,6 +206,16 @@ int hufk_fill_splitmix64(void *dst, uint64_t len, uint64_t seed, void *stream);
 /* counts[b] += the bytes of input[0 .. length) equal to b, u64 agent-scope atomic adds (count_kernels.hip); flush_bytes:
  * what a workgroup reads at most between two flushes of its 32-bit LDS counts (rounded down to 32 KiB, at least that) */
 int hufk_symbol_counts(const void *input, uint64_t length, uint64_t *counts, uint64_t flush_bytes, void *stream);
+/* Between the length pass and the encode pass of a packed launch (pack_kernels.hip): from the length pass's records
+ * `lengths`, offsets[i] = the sum of round_up((total_bits + 7) / 8, align) of the items in front of i, offsets[n_items] the
+ * total; packed[i] = items[i] with out_off = offsets[i] and out_cap = what of the item's rounded length lies in front of
+ * `capacity`; summary[0] = the total, summary[1] = the largest rounded length.  tile_sums: scratch of 2 * hufk_pack_tiles()
+ * words; tile_items: the items a workgroup scans, from hufk_pack_tile_items (asked: the tests' own number, 0: the rule). */
+uint32_t hufk_pack_tile_items(uint32_t n_items, uint32_t asked);
+uint32_t hufk_pack_tiles(uint32_t n_items, uint32_t tile_items);
+int hufk_pack_offsets(
+    const struct hufd_enc_item *items, const struct hufd_enc_result *lengths, uint32_t n_items, uint32_t tile_items, uint64_t align,
+    uint64_t capacity, uint64_t *tile_sums, uint64_t *offsets, struct hufd_enc_item *packed, uint64_t *summary, void *stream);
 
 #ifdef __cplusplus
 }

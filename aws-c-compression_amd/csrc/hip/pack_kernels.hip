@@ -1,0 +1,196 @@
+/*
+ * Packed batch encode (aws_huffman_amd_encode_plan_launch_packed, huffman_amd_packed.h): what runs between the length
+ * pass and the encode pass of such a launch.  From the length pass's result records,
+ *
+ *   len_i        = (total_bits_i + 7) / 8                       (aws_huffman_get_encoded_length, reference
+ *                                                                source/huffman.c:121-128)
+ *   reserved_i   = round_up(len_i, align)
+ *   offsets[i]   = the sum of reserved_k for k < i,  offsets[n] = the total
+ *
+ * and, for the encode pass, a second array of the plan's item records with out_off = offsets[i] and out_cap = what of
+ * reserved_i lies in front of the caller's output capacity.  The plan's own records are read, never written.
+ *
+ * Reduce, then scan -- two kernels, no workgroup waits for another, nothing to clear between launches (so a launch can be
+ * captured in a graph and replayed):
+ *   pack_tile_sums   a workgroup a tile of `tile_items` items: the tile's sum and its largest reserved length
+ *   pack_offsets     a workgroup a tile again: the sums of the tiles in front of it (read from memory, a few thousand
+ *                    words at most: the launch wrapper grows the tile with the batch), then the tile's items in rounds of
+ *                    one a thread, a workgroup scan a round; the last workgroup also writes the total and the maximum
+ * A batch of one tile goes without the first kernel.
+ */
+#include "kernels_common.hpp"
+#include "launch_common.hpp"
+
+namespace {
+
+constexpr u32 kPackThreads = 256;
+constexpr u32 kPackWaves = kPackThreads / kWave;
+constexpr u32 kPackTileItems = 1024; /* a workgroup's items: four rounds (65 536 items: 64 workgroups, a million: 1024) */
+constexpr u32 kPackMaxTiles = 8192;  /* what a workgroup of pack_offsets reads of the sums in front of it at most: 128 KiB */
+constexpr u32 kPackLdsBytes = 3 * kPackWaves * sizeof(u64);
+
+__device__ __forceinline__ u64 pack_reserved(const hufd_enc_result *lengths, u64 i, u64 align_mask) {
+    const u64 len = (lengths[i].total_bits + 7) / 8;
+    return (len + align_mask) & ~align_mask;
+}
+
+/* the workgroup's sum and maximum, in every thread; `slots`: 2 * kPackWaves words of LDS */
+__device__ __forceinline__ void pack_block_sum_max(u64 &sum, u64 &most, u64 *slots) {
+#pragma unroll
+    for (u32 d = kWave / 2; d > 0; d >>= 1) {
+        sum += __shfl_xor(sum, d);
+        const u64 o = __shfl_xor(most, d);
+        most = o > most ? o : most;
+    }
+    const u32 wave = threadIdx.x / kWave;
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+        slots[wave] = sum;
+        slots[kPackWaves + wave] = most;
+    }
+    __syncthreads();
+    sum = 0;
+    most = 0;
+#pragma unroll
+    for (u32 w = 0; w < kPackWaves; ++w) {
+        sum += slots[w];
+        most = slots[kPackWaves + w] > most ? slots[kPackWaves + w] : most;
+    }
+    __syncthreads();
+}
+
+/* block_exclusive_sum (kernels_common.hpp) over 64-bit values; `slots`: kPackWaves words of LDS */
+__device__ __forceinline__ u64 pack_block_exclusive_sum(u64 v, u64 *slots, u64 &total) {
+    const u32 lane = threadIdx.x & (kWave - 1);
+    const u32 wave = threadIdx.x / kWave;
+    u64 incl = v;
+#pragma unroll
+    for (u32 d = 1; d < kWave; d <<= 1) {
+        const u64 up = __shfl_up(incl, d);
+        if (lane >= d) {
+            incl += up;
+        }
+    }
+    if (lane == kWave - 1) {
+        slots[wave] = incl;
+    }
+    __syncthreads();
+    u64 before = 0, all = 0;
+#pragma unroll
+    for (u32 w = 0; w < kPackWaves; ++w) {
+        const u64 t = slots[w];
+        before += w < wave ? t : 0;
+        all += t;
+    }
+    __syncthreads();
+    total = all;
+    return before + incl - v;
+}
+
+/* tile_sums[2 b] = the sum of reserved_i over tile b, tile_sums[2 b + 1] = the largest of them */
+__global__ __launch_bounds__(kPackThreads) void pack_tile_sums_kernel(
+    const hufd_enc_result *lengths, u32 n_items, u32 tile_items, u64 align_mask, u64 *tile_sums) {
+    u64 *slots = reinterpret_cast<u64 *>(dyn_lds);
+    const u64 lo = (u64)blockIdx.x * tile_items;
+    const u64 hi = lo + tile_items < n_items ? lo + tile_items : n_items;
+    u64 sum = 0, most = 0;
+    for (u64 i = lo + threadIdx.x; i < hi; i += kPackThreads) {
+        const u64 r = pack_reserved(lengths, i, align_mask);
+        sum += r;
+        most = r > most ? r : most;
+    }
+    pack_block_sum_max(sum, most, slots);
+    if (threadIdx.x == 0) {
+        tile_sums[2 * (u64)blockIdx.x] = sum;
+        tile_sums[2 * (u64)blockIdx.x + 1] = most;
+    }
+}
+
+/* offsets[0 .. n_items], packed[0 .. n_items), summary[0] = the total, summary[1] = the largest reserved length */
+__global__ __launch_bounds__(kPackThreads) void pack_offsets_kernel(
+    const hufd_enc_item *items, const hufd_enc_result *lengths, u32 n_items, u32 tile_items, u64 align_mask, u64 capacity,
+    const u64 *tile_sums, u64 *offsets, hufd_enc_item *packed, u64 *summary) {
+    u64 *slots = reinterpret_cast<u64 *>(dyn_lds);
+    /* where the tile starts: the sums of the tiles in front (and, for the last workgroup's sake, their maximum) */
+    u64 at = 0, most = 0;
+    for (u32 k = threadIdx.x; k < blockIdx.x; k += kPackThreads) {
+        at += tile_sums[2 * (u64)k];
+        const u64 m = tile_sums[2 * (u64)k + 1];
+        most = m > most ? m : most;
+    }
+    pack_block_sum_max(at, most, slots + kPackWaves);
+    const u64 lo = (u64)blockIdx.x * tile_items;
+    const u64 hi = lo + tile_items < n_items ? lo + tile_items : n_items;
+    u64 mine = 0; /* the largest reserved length this thread met */
+    for (u64 round = lo; round < hi; round += kPackThreads) { /* (the same trips in every thread: the scan has barriers) */
+        const u64 i = round + threadIdx.x;
+        const u64 reserved = i < hi ? pack_reserved(lengths, i, align_mask) : 0;
+        u64 total = 0;
+        const u64 off = at + pack_block_exclusive_sum(reserved, slots, total);
+        if (i < hi) {
+            const u64 room = capacity > off ? capacity - off : 0;
+            const hufd_enc_item *from = items + i;
+            hufd_enc_item *to = packed + i; /* (field by field: the record copied as a whole went through scratch memory) */
+            to->in_off = from->in_off;
+            to->in_len = from->in_len;
+            to->out_off = off;
+            to->out_cap = reserved < room ? reserved : room;
+            to->ovf_pattern = from->ovf_pattern;
+            to->ovf_bits = from->ovf_bits;
+            to->eos_padding = from->eos_padding;
+            to->first_seg = from->first_seg;
+            to->n_segs = from->n_segs;
+            to->tiny = from->tiny;
+            offsets[i] = off; /* (never clipped: what the caller would have needed) */
+            mine = reserved > mine ? reserved : mine;
+        }
+        at += total;
+    }
+    if (blockIdx.x == gridDim.x - 1) {
+        u64 unused = 0;
+        pack_block_sum_max(unused, mine, slots + kPackWaves);
+        if (threadIdx.x == 0) {
+            offsets[n_items] = at;
+            summary[0] = at;
+            summary[1] = mine > most ? mine : most;
+        }
+    }
+}
+
+} /* namespace */
+
+extern "C" {
+
+uint32_t hufk_pack_tile_items(uint32_t n_items, uint32_t asked) {
+    if (asked) {
+        return asked;
+    }
+    /* at most kPackMaxTiles tiles, of whole rounds */
+    const uint64_t per = ((uint64_t)n_items + kPackMaxTiles - 1) / kPackMaxTiles;
+    const uint64_t rounded = (per + kPackThreads - 1) / kPackThreads * kPackThreads;
+    return (uint32_t)(rounded > kPackTileItems ? rounded : kPackTileItems);
+}
+
+uint32_t hufk_pack_tiles(uint32_t n_items, uint32_t tile_items) {
+    return (uint32_t)(((uint64_t)n_items + tile_items - 1) / tile_items);
+}
+
+int hufk_pack_offsets(
+    const struct hufd_enc_item *items, const struct hufd_enc_result *lengths, uint32_t n_items, uint32_t tile_items, uint64_t align,
+    uint64_t capacity, uint64_t *tile_sums, uint64_t *offsets, struct hufd_enc_item *packed, uint64_t *summary, void *stream) {
+    if (n_items == 0 || tile_items == 0) {
+        return 0;
+    }
+    const uint32_t tiles = hufk_pack_tiles(n_items, tile_items);
+    const u64 align_mask = align - 1;
+    if (tiles > 1) {
+        hipLaunchKernelGGL(
+            pack_tile_sums_kernel, dim3(tiles - 1), dim3(kPackThreads), kPackLdsBytes, (hipStream_t)stream, lengths, n_items, tile_items,
+            align_mask, tile_sums); /* (nobody reads the last tile's sums) */
+    }
+    hipLaunchKernelGGL(
+        pack_offsets_kernel, dim3(tiles), dim3(kPackThreads), kPackLdsBytes, (hipStream_t)stream, items, lengths, n_items, tile_items,
+        align_mask, capacity, (const u64 *)tile_sums, offsets, packed, summary);
+    return (int)hipGetLastError();
+}
+
+} /* extern "C" */

@@ -8,6 +8,7 @@
 #include "engine.h"
 
 #include <aws/compression/huffman_amd_build.h>
+#include <aws/compression/huffman_amd_packed.h>
 
 #include <stdlib.h>
 #include <string.h>
@@ -718,6 +719,8 @@ static int enc_plan_fill(
     memset(&p->stats, 0, sizeof(p->stats));
     p->largest_out_cap = stats.largest_out_cap;
     p->most_overflow_bits = stats.worst_bits;
+    p->longest_in_len = stats.longest;
+    p->packed = p->packed_sized = false;
     if (n_items >= PLAN_ON_DEVICE_MIN_ITEMS && n_items < 0xFFFFFFFFull && stats.shortest >= 1 && stats.longest <= tiny_limit &&
         stats.worst_bits <= 32) {
         /* every item is one thread's work (enc_item_is_tiny): no segments, no lists to make -- the caller's records go to the
@@ -942,6 +945,8 @@ static int enc_plan_fill_on_device(struct aws_huffman_amd_encode_plan *p, const 
     memset(&p->stats, 0, sizeof(p->stats));
     p->largest_out_cap = 0;
     p->most_overflow_bits = 0;
+    p->longest_in_len = 0;
+    p->packed = p->packed_sized = false;
     if (n_items == 0) {
         return AWS_OP_SUCCESS;
     }
@@ -979,6 +984,7 @@ static int enc_plan_fill_on_device(struct aws_huffman_amd_encode_plan *p, const 
     p->n_solo = (uint32_t)t.totals[2];
     p->largest_out_cap = t.largest_out_cap;
     p->most_overflow_bits = t.worst_bits;
+    p->longest_in_len = t.longest;
     p->stats.items = n_items;
     p->stats.thread_limit = t.tiny_limit;
     p->stats.by_thread = t.totals[1];
@@ -1044,6 +1050,7 @@ void aws_huffman_amd_encode_plan_destroy(struct aws_huffman_amd_encode_plan *p) 
         }
         ON_DEVICE(eng->device);
         enc_plan_release_device(p);
+        hufs_free(p->d_packed_arena);
         hufs_free(p->d_plan_scratch);
         hufs_event_destroy(p->done_event);
         free(p);
@@ -1059,8 +1066,10 @@ int aws_huffman_amd_encode_plan_launch(
     return aws_huffman_amd_encode_plan_launch_staged(p, device_input, device_output, length_only, stream, NULL);
 }
 
-int aws_huffman_amd_encode_plan_launch_staged(
+/* one launch of the plan's lists over `items`: the plan's own records, or the ones a packed launch has rewritten */
+static int enc_plan_launch_items(
     struct aws_huffman_amd_encode_plan *p,
+    const struct hufd_enc_item *items,
     const void *device_input,
     void *device_output,
     bool length_only,
@@ -1070,7 +1079,7 @@ int aws_huffman_amd_encode_plan_launch_staged(
     struct hufk_encode_args a;
     memset(&a, 0, sizeof(a));
     a.tables = p->engine->tables;
-    a.items = p->d_items;
+    a.items = items;
     a.n_items = p->n_items;
     a.segs = p->d_segs;
     a.n_segs = p->n_segs;
@@ -1113,6 +1122,135 @@ int aws_huffman_amd_encode_plan_launch_staged(
         err = plan_mark_done(&p->done_event, &p->done_on_engine_stream, p->engine, stream);
     }
     return err ? raise_hip(err) : AWS_OP_SUCCESS;
+}
+
+int aws_huffman_amd_encode_plan_launch_staged(
+    struct aws_huffman_amd_encode_plan *p,
+    const void *device_input,
+    void *device_output,
+    bool length_only,
+    void *stream,
+    void **stage_events) {
+    if (!length_only) {
+        p->packed = false; /* (the output lies where the plan's own records say) */
+    }
+    return enc_plan_launch_items(p, p->d_items, device_input, device_output, length_only, stream, stage_events);
+}
+
+/* ------------------------------------------------------------------ packed launches (huffman_amd_packed.h) */
+
+static uint32_t s_pack_tile_items = 0;
+
+void aws_huffman_amd_testing_set_pack_tile_items(uint32_t items) {
+    __atomic_store_n(&s_pack_tile_items, items, __ATOMIC_RELAXED);
+}
+
+/* the second record array, the scan's tile sums and its summary words for this many items and tiles (grown, never
+ * shrunk): an allocation, so not inside a graph capture -- the first packed launch of a plan, or of more items */
+static int enc_plan_reserve_packed(struct aws_huffman_amd_encode_plan *p, size_t n_items, size_t n_tiles) {
+    if (p->d_packed_arena && n_items <= p->cap_packed_items && n_tiles <= p->cap_pack_tiles) {
+        return 0;
+    }
+    hufs_free(p->d_packed_arena); /* (waits for what still reads it) */
+    p->d_packed_arena = NULL;
+    p->cap_packed_items = p->cap_pack_tiles = 0;
+    const size_t ci = n_items > p->cap_items ? n_items : p->cap_items; /* as many as the plan's own array: a reset within it allocates nothing */
+    size_t total = 0;
+    const size_t at_items = arena_cut(&total, ci * sizeof(struct hufd_enc_item));
+    const size_t at_sums = arena_cut(&total, 2 * n_tiles * sizeof(uint64_t));
+    const size_t at_summary = arena_cut(&total, 2 * sizeof(uint64_t));
+    p->d_packed_arena = hufs_malloc(total);
+    if (!p->d_packed_arena) {
+        return 2;
+    }
+    p->d_packed_items = (void *)((uint8_t *)p->d_packed_arena + at_items);
+    p->d_pack_tile_sums = (void *)((uint8_t *)p->d_packed_arena + at_sums);
+    p->d_pack_summary = (void *)((uint8_t *)p->d_packed_arena + at_summary);
+    p->cap_packed_items = ci;
+    p->cap_pack_tiles = n_tiles;
+    return 0;
+}
+
+int aws_huffman_amd_encode_plan_launch_packed(
+    struct aws_huffman_amd_encode_plan *p,
+    const void *device_input,
+    void *device_output,
+    uint64_t output_capacity,
+    uint64_t *device_offsets,
+    uint32_t align,
+    void *stream) {
+
+    if (!p || !device_offsets || ((uintptr_t)device_offsets & 7u) || align == 0 || align > 4096 || (align & (align - 1)) ||
+        (!device_output && output_capacity)) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    void *st = stream ? stream : p->engine->stream;
+    if (p->n_items == 0) {
+        ON_DEVICE(p->engine->device);
+        const int e = hufs_memset(device_offsets, 0, sizeof(uint64_t), st);
+        if (e) {
+            return raise_hip(e);
+        }
+        p->packed = false;
+        p->packed_sized = true;
+        return AWS_OP_SUCCESS;
+    }
+    const uint32_t tile_items = hufk_pack_tile_items(p->n_items, __atomic_load_n(&s_pack_tile_items, __ATOMIC_RELAXED));
+    {
+        ON_DEVICE(p->engine->device);
+        const int e = enc_plan_reserve_packed(p, p->n_items, hufk_pack_tiles(p->n_items, tile_items));
+        if (e) {
+            return raise_hip(e);
+        }
+    }
+    /* the lengths (into the plan's result records), the offsets and the second record array from them, the encode pass over
+     * that array (its records replace the lengths): three stages on one stream */
+    if (enc_plan_launch_items(p, p->d_items, device_input, device_output, true, stream, NULL)) {
+        return AWS_OP_ERR;
+    }
+    {
+        ON_DEVICE(p->engine->device);
+        const int e = hufk_pack_offsets(
+            p->d_items, p->d_results, p->n_items, tile_items, align, output_capacity, p->d_pack_tile_sums, device_offsets,
+            p->d_packed_items, p->d_pack_summary, st);
+        if (e) {
+            return raise_hip(e);
+        }
+    }
+    if (enc_plan_launch_items(p, p->d_packed_items, device_input, device_output, false, stream, NULL)) {
+        return AWS_OP_ERR;
+    }
+    p->packed = true;
+    p->packed_sized = true;
+    return AWS_OP_SUCCESS;
+}
+
+int aws_huffman_amd_encode_plan_packed_size(
+    struct aws_huffman_amd_encode_plan *p,
+    uint64_t *total_bytes,
+    uint64_t *longest_item_bytes,
+    void *stream) {
+
+    if (!p || !p->packed_sized) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    uint64_t summary[2] = {0, 0};
+    ON_DEVICE(p->engine->device);
+    void *st = stream ? stream : p->engine->stream;
+    int err = p->n_items ? hufs_copy_d2h(summary, p->d_pack_summary, sizeof(summary), st) : 0;
+    if (!err) {
+        err = hufs_stream_sync(st);
+    }
+    if (err) {
+        return raise_hip(err);
+    }
+    if (total_bytes) {
+        *total_bytes = summary[0];
+    }
+    if (longest_item_bytes) {
+        *longest_item_bytes = summary[1];
+    }
+    return AWS_OP_SUCCESS;
 }
 
 int aws_huffman_amd_encode_plan_raw_results(
@@ -2111,7 +2249,13 @@ int aws_huffman_amd_decode_plan_from_encode(
     /* Whatever the launch produced, every item must be ONE THREAD's work for the decoder (then the plan has no chunk
      * geometry, which only the host can lay out): the most bytes an item can have left is its output capacity.  The same
      * rule as for a plan from host records (dec_tiny_limit), with the capacities for the lengths. */
-    const uint64_t n_items = encoded->n_items, longest = encoded->largest_out_cap;
+    /* (after a packed launch the items' own capacities were not used: the bound is what the longest item can come to --
+     * its symbols at the longest code, and the carried bits --, known here without a wait; the records the decode plan is
+     * made from are the ones that launch wrote behind) */
+    const uint64_t packed_bound =
+        (encoded->longest_in_len * (uint64_t)encoded->engine->tables.enc_max_bits + encoded->most_overflow_bits + 7) / 8;
+    const struct hufd_enc_item *enc_items = encoded->packed ? encoded->d_packed_items : encoded->d_items;
+    const uint64_t n_items = encoded->n_items, longest = encoded->packed ? packed_bound : encoded->largest_out_cap;
     bool thread_each = n_items >= 1 && n_items < 0xFFFFFFFFull && longest <= HUFD_TINY_FEW_BYTES;
     {
         static const uint64_t classes[2] = {HUFD_DEC_COOP_BYTES, HUFD_DEC_TINY_BYTES};
@@ -2125,7 +2269,7 @@ int aws_huffman_amd_decode_plan_from_encode(
         struct hufd_item_source src;
         memset(&src, 0, sizeof(src));
         src.kind = HUFD_ITEMS_FROM_ENCODE;
-        src.enc_items = encoded->d_items;
+        src.enc_items = enc_items;
         src.enc_results = encoded->d_results;
         return dec_plan_fill_on_device(p, &src, (size_t)n_items, stream);
     }
@@ -2138,7 +2282,7 @@ int aws_huffman_amd_decode_plan_from_encode(
     int e = dec_plan_reserve(p, n_items, 0, 0, 0);
     if (!e) {
         e = hufk_decode_plan_from_encode(
-            encoded->d_items, encoded->d_results, (uint32_t)n_items, p->d_items, p->d_tiny, stream ? stream : eng->stream);
+            enc_items, encoded->d_results, (uint32_t)n_items, p->d_items, p->d_tiny, stream ? stream : eng->stream);
     }
     if (e) {
         return raise_hip(e);

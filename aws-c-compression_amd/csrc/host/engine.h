@@ -100,6 +100,17 @@ struct aws_huffman_amd_encode_plan {
     /* of the items as they were given: what aws_huffman_amd_decode_plan_from_encode asks before it chains a decode plan */
     uint64_t largest_out_cap; /* the most encoded bytes an item can leave */
     uint32_t most_overflow_bits;
+    uint64_t longest_in_len; /* symbols of the longest item */
+    /* packed launches (huffman_amd_packed.h): a second array of item records -- the plan's own with out_off / out_cap
+     * rewritten by hufk_pack_offsets --, the scan's tile sums and its two summary words; ONE allocation, made by the first
+     * packed launch and grown by a later one of more items or tiles */
+    void *d_packed_arena;
+    struct hufd_enc_item *d_packed_items; /* [cap_packed_items] */
+    uint64_t *d_pack_tile_sums;           /* [2 * cap_pack_tiles] */
+    uint64_t *d_pack_summary;             /* [2]: the total, the largest reserved length */
+    size_t cap_packed_items, cap_pack_tiles;
+    bool packed;       /* the last encode launch was a packed one: its output lies where d_packed_items say */
+    bool packed_sized; /* ... and one was made since the plan was filled: d_pack_summary is of these items */
 };
 
 struct aws_huffman_amd_decode_plan {
