@@ -476,14 +476,15 @@ int hufk_decode_plan_from_encode(
     return (int)hipGetLastError();
 }
 
-int hufk_decode_launch(const struct hufk_decode_args *a, void *stream) {
-    hipStream_t st = (hipStream_t)stream;
+/* the stages of a launch on its stream; pk: a packed launch (hufk_decode_launch_packed), NULL: a plain one */
+static int decode_launch_stages(const struct hufk_decode_args *a, const struct hufk_decode_pack *pk, hipStream_t st) {
     if (a->n_items == 0) {
         return 0;
     }
     const uint32_t ns = a->tables.n_states;
     stage_mark(a->stage_events, 0, st);
-    if (a->n_fixed_blocks && a->tables.fixed_bits) {
+    const bool fixed = a->n_fixed_blocks && a->tables.fixed_bits;
+    if (fixed) {
         (void)hipMemsetAsync(a->states, 0xFF, (size_t)a->n_items * sizeof(hufd_dec_item_state), st);
     }
     /* the builds of the row-synchronous kernels: a decode table of up to 10 bits with 3 or 4 certain steps a row (codes
@@ -495,6 +496,20 @@ int hufk_decode_launch(const struct hufk_decode_args *a, void *stream) {
     const uint32_t sure = lb_of_launch == 10 ? (sure_of_coder > 4 ? 4u : sure_of_coder) : (sure_of_coder > 2 ? 2u : sure_of_coder);
     if (a->n_chunks && (a->tables.max_bits > HUFD_DEC_MAX_LUT_BITS || (lb_of_launch == 10 ? sure < 3 : sure != 2))) {
         return (int)hipErrorInvalidValue; /* (a plan has chunks only for a decode table of up to 12 bits; see row_walk for the steps) */
+    }
+    /* a packed launch: the kernels that walk and write an item in one go first run against records without room -- their
+     * counts are what the offsets are made from --, and again behind the offsets */
+    const bool one_go = a->n_tiny || a->n_deep || fixed;
+    struct hufk_decode_args counting;
+    const struct hufk_decode_args *items_pass = a;
+    if (pk && one_go) {
+        const int e = hufk_unpack_blank(a->items, a->n_items, pk->items, st);
+        if (e) {
+            return e;
+        }
+        counting = *a;
+        counting.items = pk->items;
+        items_pass = &counting;
     }
     decode_launch_state state = {lb_of_launch, sure, false};
     if (a->n_chunks) {
@@ -509,7 +524,7 @@ int hufk_decode_launch(const struct hufk_decode_args *a, void *stream) {
             dec_scan_small_kernel, dim3((a->n_items + 255) / 256), dim3(256), 0, st, a->items, a->n_items, ns, a->chunk_fn,
             a->chunk_entry, a->chunk_base, a->states, a->results);
     }
-    hufk_host::decode_items_stage(a, st);
+    hufk_host::decode_items_stage(items_pass, st);
     if (a->n_large) {
         const uint32_t lds = scan_run_lds_bytes(ns);
         hipLaunchKernelGGL(
@@ -520,11 +535,41 @@ int hufk_decode_launch(const struct hufk_decode_args *a, void *stream) {
     }
     hufk_host::decode_sync_true_stage(a, st, state);
     stage_mark(a->stage_events, 2, st);
+    struct hufk_decode_args placed;
+    if (pk) {
+        /* every item's record now holds its symbol count: the offsets, the records with the items' places, the kernels
+         * that write there */
+        const int e = hufk_unpack_offsets(
+            a->items, a->results, a->n_items, pk->tile_items, pk->align, pk->capacity, pk->tile_sums, pk->offsets, pk->items,
+            pk->summary, a->chunk_rec, a->n_chunks, pk->chunk_rec, st);
+        if (e) {
+            return e;
+        }
+        placed = *a;
+        placed.items = pk->items;
+        placed.chunk_rec = pk->chunk_rec;
+        placed.tail_stage_bytes = pk->tail_stage_bytes;
+        a = &placed;
+        if (one_go) {
+            if (fixed) {
+                (void)hipMemsetAsync(a->states, 0xFF, (size_t)a->n_items * sizeof(hufd_dec_item_state), st);
+            }
+            hufk_host::decode_items_stage(a, st);
+        }
+    }
     if (a->n_chunks) {
         hufk_host::decode_emit_stage(a, st, state);
     }
     stage_mark(a->stage_events, 3, st);
     return (int)hipGetLastError();
+}
+
+int hufk_decode_launch(const struct hufk_decode_args *a, void *stream) {
+    return decode_launch_stages(a, nullptr, (hipStream_t)stream);
+}
+
+int hufk_decode_launch_packed(const struct hufk_decode_args *a, const struct hufk_decode_pack *pack, void *stream) {
+    return decode_launch_stages(a, pack, (hipStream_t)stream);
 }
 
 #ifdef HUFD_STAMPS

@@ -221,10 +221,11 @@ struct hufd_chunk_rec {
 };
 
 /* Where the items of a plan that is made on the device come from (plan_kernels.hip): the caller's records in DEVICE memory,
- * a stride, or what an encode launch left */
+ * a stride, what an encode launch left, or a packed buffer's offsets (decode) */
 #define HUFD_ITEMS_DEVICE_ARRAY 0u
 #define HUFD_ITEMS_STRIDED 1u
 #define HUFD_ITEMS_FROM_ENCODE 2u
+#define HUFD_ITEMS_PACKED_INPUT 3u
 struct hufd_item_source {
     uint32_t kind;
     uint32_t first_bit;   /* strided, decode */
@@ -236,6 +237,10 @@ struct hufd_item_source {
     /* from an encode plan's last launch: its item records and result records */
     const struct hufd_enc_item *enc_items;
     const struct hufd_enc_result *enc_results;
+    /* a packed input (decode): item i reads packed_lengths[i] bytes at packed_offsets[i] -- without lengths, up to
+     * packed_offsets[i + 1] -- from bit 0, and has no room of its own (such a plan is for packed launches) */
+    const uint64_t *packed_offsets;
+    const uint64_t *packed_lengths;
 };
 
 #endif /* HUFFMAN_AMD_DEVICE_TYPES_H */

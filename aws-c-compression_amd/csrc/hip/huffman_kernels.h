@@ -143,6 +143,21 @@ int hufk_encode_one_pass_applies(const struct hufd_tables *tables);
 uint64_t hufk_encode_zero_bytes(uint32_t n_segs, uint32_t n_items);
 int hufk_encode_launch(const struct hufk_encode_args *args, void *stream);
 int hufk_decode_launch(const struct hufk_decode_args *args, void *stream);
+/* A packed launch (huffman_amd_packed.h): the plan's items decoded back to back, each to as many symbols as its stream
+ * holds.  The sync stage, the scans, the offsets from the scans' symbol counts (hufk_unpack_offsets), the emit stage behind
+ * them: the walk over the encoded bytes runs once.  The items without chunks, whose kernels walk and write in one go, run
+ * twice: against no room at all for their counts, then against their places. */
+struct hufk_decode_pack {
+    uint32_t tile_items; /* hufk_pack_tile_items */
+    uint32_t tail_stage_bytes; /* hufk_decode_args.tail_stage_bytes for the packed capacities (the plan's own is for its own) */
+    uint64_t align, capacity;
+    uint64_t *tile_sums; /* scratch: 2 * hufk_pack_tiles() words */
+    uint64_t *offsets;   /* [n_items + 1], the caller's */
+    uint64_t *summary;   /* [2]: the total, the largest rounded count */
+    struct hufd_dec_item *items;      /* [n_items] the second record array: args->items with out_off / out_cap rewritten */
+    struct hufd_chunk_rec *chunk_rec; /* [n_chunks] ... and args->chunk_rec with the same */
+};
+int hufk_decode_launch_packed(const struct hufk_decode_args *args, const struct hufk_decode_pack *pack, void *stream);
 /* a plan of items that are all one thread's work: the kernels' item records and the list of such items (= all of them) from
  * the caller's records, copied to the device as they are (struct hufd_raw_dec_item / hufd_raw_enc_item) */
 int hufk_decode_plan_tiny_items(const void *raw_items, uint32_t n_items, struct hufd_dec_item *items, uint32_t *tiny_list, void *stream);
@@ -216,6 +231,15 @@ uint32_t hufk_pack_tiles(uint32_t n_items, uint32_t tile_items);
 int hufk_pack_offsets(
     const struct hufd_enc_item *items, const struct hufd_enc_result *lengths, uint32_t n_items, uint32_t tile_items, uint64_t align,
     uint64_t capacity, uint64_t *tile_sums, uint64_t *offsets, struct hufd_enc_item *packed, uint64_t *summary, void *stream);
+/* The same for a packed decode launch, from the scans' records `counts`: offsets[i + 1] = round_up(offsets[i] +
+ * total_symbols_i, align); packed[i] = items[i] with out_off = offsets[i] and out_cap = total_symbols_i where the item's
+ * symbols all lie in front of `capacity`, 0 where not; packed_rec[c] = chunk_rec[c] with its item's new out_off / out_cap.
+ * _blank: packed[i] = items[i] with no room (what the walk that only counts is given). */
+int hufk_unpack_blank(const struct hufd_dec_item *items, uint32_t n_items, struct hufd_dec_item *packed, void *stream);
+int hufk_unpack_offsets(
+    const struct hufd_dec_item *items, const struct hufd_dec_result *counts, uint32_t n_items, uint32_t tile_items, uint64_t align,
+    uint64_t capacity, uint64_t *tile_sums, uint64_t *offsets, struct hufd_dec_item *packed, uint64_t *summary,
+    const struct hufd_chunk_rec *chunk_rec, uint32_t n_chunks, struct hufd_chunk_rec *packed_rec, void *stream);
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,17 @@
  *                    words at most: the launch wrapper grows the tile with the batch), then the tile's items in rounds of
  *                    one a thread, a workgroup scan a round; the last workgroup also writes the total and the maximum
  * A batch of one tile goes without the first kernel.
+ *
+ * Packed batch decode (aws_huffman_amd_decode_plan_launch_packed) is the mirror: the same two kernels over the symbol counts
+ * the decode scan left (hufd_dec_result.total_symbols), between the scan and the emit stage of such a launch,
+ *
+ *   sym_i        = what the reference's aws_huffman_decode writes for item i when it never runs out of room
+ *   offsets[i+1] = round_up(offsets[i] + sym_i, align)
+ *
+ * with out_cap = sym_i for an item whose symbols all lie in front of the caller's capacity and 0 for any other, and
+ *   unpack_records   a thread a chunk: the plan's per-chunk records with their item's new place, for the emit kernels; or
+ *                    a thread an item: the second record array with no room at all, for the walk that only counts (the
+ *                    kernels that walk and write an item in one go run twice in a packed launch)
  */
 #include "kernels_common.hpp"
 #include "launch_common.hpp"
@@ -29,9 +40,58 @@ constexpr u32 kPackTileItems = 1024; /* a workgroup's items: four rounds (65 536
 constexpr u32 kPackMaxTiles = 8192;  /* what a workgroup of pack_offsets reads of the sums in front of it at most: 128 KiB */
 constexpr u32 kPackLdsBytes = 3 * kPackWaves * sizeof(u64);
 
-__device__ __forceinline__ u64 pack_reserved(const hufd_enc_result *lengths, u64 i, u64 align_mask) {
-    const u64 len = (lengths[i].total_bits + 7) / 8;
-    return (len + align_mask) & ~align_mask;
+/* The two kinds of batch the two kernels take (`decode`: a launch argument, the same in every thread -- not a second
+ * build of each kernel): the length of an item in its first pass's record, and the item's record for the second pass */
+struct pack_encode {
+    typedef hufd_enc_item item;
+    typedef hufd_enc_result measured;
+    static __device__ __forceinline__ u64 length(const measured *lengths, u64 i) {
+        return (lengths[i].total_bits + 7) / 8;
+    }
+    /* (field by field: the record copied as a whole went through scratch memory) */
+    static __device__ __forceinline__ void place(const item *from, item *to, u64 off, u64 len, u64 reserved, u64 capacity) {
+        (void)len;
+        const u64 room = capacity > off ? capacity - off : 0;
+        to->in_off = from->in_off;
+        to->in_len = from->in_len;
+        to->out_off = off;
+        to->out_cap = reserved < room ? reserved : room;
+        to->ovf_pattern = from->ovf_pattern;
+        to->ovf_bits = from->ovf_bits;
+        to->eos_padding = from->eos_padding;
+        to->first_seg = from->first_seg;
+        to->n_segs = from->n_segs;
+        to->tiny = from->tiny;
+    }
+};
+struct pack_decode {
+    typedef hufd_dec_item item;
+    typedef hufd_dec_result measured;
+    static __device__ __forceinline__ u64 length(const measured *counts, u64 i) {
+        return counts[i].total_symbols;
+    }
+    /* all of the item's symbols or none: there is no partial room (the caller allocates the total and launches again) */
+    static __device__ __forceinline__ void place(const item *from, item *to, u64 off, u64 len, u64 reserved, u64 capacity) {
+        (void)reserved;
+        const bool fits = off <= capacity && len <= capacity - off;
+        to->in_off = from->in_off;
+        to->in_len = from->in_len;
+        to->out_off = off;
+        to->out_cap = fits ? len : 0;
+        to->first_bit = from->first_bit;
+        to->first_chunk = from->first_chunk;
+        to->n_chunks = from->n_chunks;
+        to->tiny = from->tiny;
+    }
+};
+
+__device__ __forceinline__ u64 pack_length(const void *lengths, u32 decode, u64 i) {
+    return decode ? pack_decode::length(reinterpret_cast<const pack_decode::measured *>(lengths), i)
+                  : pack_encode::length(reinterpret_cast<const pack_encode::measured *>(lengths), i);
+}
+
+__device__ __forceinline__ u64 pack_reserved(const void *lengths, u32 decode, u64 i, u64 align_mask) {
+    return (pack_length(lengths, decode, i) + align_mask) & ~align_mask;
 }
 
 /* the workgroup's sum and maximum, in every thread; `slots`: 2 * kPackWaves words of LDS */
@@ -88,13 +148,13 @@ __device__ __forceinline__ u64 pack_block_exclusive_sum(u64 v, u64 *slots, u64 &
 
 /* tile_sums[2 b] = the sum of reserved_i over tile b, tile_sums[2 b + 1] = the largest of them */
 __global__ __launch_bounds__(kPackThreads) void pack_tile_sums_kernel(
-    const hufd_enc_result *lengths, u32 n_items, u32 tile_items, u64 align_mask, u64 *tile_sums) {
+    const void *lengths, u32 decode, u32 n_items, u32 tile_items, u64 align_mask, u64 *tile_sums) {
     u64 *slots = reinterpret_cast<u64 *>(dyn_lds);
     const u64 lo = (u64)blockIdx.x * tile_items;
     const u64 hi = lo + tile_items < n_items ? lo + tile_items : n_items;
     u64 sum = 0, most = 0;
     for (u64 i = lo + threadIdx.x; i < hi; i += kPackThreads) {
-        const u64 r = pack_reserved(lengths, i, align_mask);
+        const u64 r = pack_reserved(lengths, decode, i, align_mask);
         sum += r;
         most = r > most ? r : most;
     }
@@ -107,8 +167,8 @@ __global__ __launch_bounds__(kPackThreads) void pack_tile_sums_kernel(
 
 /* offsets[0 .. n_items], packed[0 .. n_items), summary[0] = the total, summary[1] = the largest reserved length */
 __global__ __launch_bounds__(kPackThreads) void pack_offsets_kernel(
-    const hufd_enc_item *items, const hufd_enc_result *lengths, u32 n_items, u32 tile_items, u64 align_mask, u64 capacity,
-    const u64 *tile_sums, u64 *offsets, hufd_enc_item *packed, u64 *summary) {
+    const void *items, const void *lengths, u32 decode, u32 n_items, u32 tile_items, u64 align_mask, u64 capacity,
+    const u64 *tile_sums, u64 *offsets, void *packed, u64 *summary) {
     u64 *slots = reinterpret_cast<u64 *>(dyn_lds);
     /* where the tile starts: the sums of the tiles in front (and, for the last workgroup's sake, their maximum) */
     u64 at = 0, most = 0;
@@ -123,23 +183,19 @@ __global__ __launch_bounds__(kPackThreads) void pack_offsets_kernel(
     u64 mine = 0; /* the largest reserved length this thread met */
     for (u64 round = lo; round < hi; round += kPackThreads) { /* (the same trips in every thread: the scan has barriers) */
         const u64 i = round + threadIdx.x;
-        const u64 reserved = i < hi ? pack_reserved(lengths, i, align_mask) : 0;
+        const u64 reserved = i < hi ? pack_reserved(lengths, decode, i, align_mask) : 0;
         u64 total = 0;
         const u64 off = at + pack_block_exclusive_sum(reserved, slots, total);
         if (i < hi) {
-            const u64 room = capacity > off ? capacity - off : 0;
-            const hufd_enc_item *from = items + i;
-            hufd_enc_item *to = packed + i; /* (field by field: the record copied as a whole went through scratch memory) */
-            to->in_off = from->in_off;
-            to->in_len = from->in_len;
-            to->out_off = off;
-            to->out_cap = reserved < room ? reserved : room;
-            to->ovf_pattern = from->ovf_pattern;
-            to->ovf_bits = from->ovf_bits;
-            to->eos_padding = from->eos_padding;
-            to->first_seg = from->first_seg;
-            to->n_segs = from->n_segs;
-            to->tiny = from->tiny;
+            if (decode) {
+                pack_decode::place(
+                    reinterpret_cast<const pack_decode::item *>(items) + i, reinterpret_cast<pack_decode::item *>(packed) + i, off,
+                    pack_length(lengths, decode, i), reserved, capacity);
+            } else {
+                pack_encode::place(
+                    reinterpret_cast<const pack_encode::item *>(items) + i, reinterpret_cast<pack_encode::item *>(packed) + i, off, 0,
+                    reserved, capacity);
+            }
             offsets[i] = off; /* (never clipped: what the caller would have needed) */
             mine = reserved > mine ? reserved : mine;
         }
@@ -154,6 +210,51 @@ __global__ __launch_bounds__(kPackThreads) void pack_offsets_kernel(
             summary[1] = mine > most ? mine : most;
         }
     }
+}
+
+/* The records of a packed decode launch that are not the scan's to write, a thread each (ONE kernel for both uses):
+ *   chunk_rec == nullptr   packed[i] = items[i] with no room at all, i < n: what the kernels that walk and write in one go
+ *                          count against
+ *   otherwise              packed_rec[c] = chunk_rec[c] with out_off / out_cap of its item's packed record, c < n */
+__global__ __launch_bounds__(kPackThreads) void unpack_records_kernel(
+    const hufd_dec_item *items, hufd_dec_item *packed, const hufd_chunk_rec *chunk_rec, hufd_chunk_rec *packed_rec, u32 n) {
+    const u32 k = blockIdx.x * kPackThreads + threadIdx.x;
+    if (k >= n) {
+        return;
+    }
+    if (chunk_rec == nullptr) {
+        pack_decode::place(items + k, packed + k, 0, 1, 0, 0);
+        return;
+    }
+    const hufd_chunk_rec *from = chunk_rec + k;
+    hufd_chunk_rec *to = packed_rec + k;
+    const u32 item = from->item;
+    to->src_off = from->src_off;
+    to->out_off = packed[item].out_off;
+    to->out_cap = packed[item].out_cap;
+    to->valid = from->valid;
+    to->item = item;
+    to->entry_bit = from->entry_bit;
+    to->reserved = 0;
+}
+
+int pack_offsets_launch(
+    const void *items, const void *lengths, uint32_t decode, uint32_t n_items, uint32_t tile_items, uint64_t align,
+    uint64_t capacity, uint64_t *tile_sums, uint64_t *offsets, void *packed, uint64_t *summary, hipStream_t st) {
+    if (n_items == 0 || tile_items == 0) {
+        return 0;
+    }
+    const uint32_t tiles = hufk_pack_tiles(n_items, tile_items);
+    const u64 align_mask = align - 1;
+    if (tiles > 1) {
+        hipLaunchKernelGGL(
+            pack_tile_sums_kernel, dim3(tiles - 1), dim3(kPackThreads), kPackLdsBytes, st, lengths, decode, n_items, tile_items,
+            align_mask, tile_sums); /* (nobody reads the last tile's sums) */
+    }
+    hipLaunchKernelGGL(
+        pack_offsets_kernel, dim3(tiles), dim3(kPackThreads), kPackLdsBytes, st, items, lengths, decode, n_items, tile_items,
+        align_mask, capacity, (const u64 *)tile_sums, offsets, packed, summary);
+    return (int)hipGetLastError();
 }
 
 } /* namespace */
@@ -177,19 +278,32 @@ uint32_t hufk_pack_tiles(uint32_t n_items, uint32_t tile_items) {
 int hufk_pack_offsets(
     const struct hufd_enc_item *items, const struct hufd_enc_result *lengths, uint32_t n_items, uint32_t tile_items, uint64_t align,
     uint64_t capacity, uint64_t *tile_sums, uint64_t *offsets, struct hufd_enc_item *packed, uint64_t *summary, void *stream) {
-    if (n_items == 0 || tile_items == 0) {
+    return pack_offsets_launch(
+        items, lengths, 0u, n_items, tile_items, align, capacity, tile_sums, offsets, packed, summary, (hipStream_t)stream);
+}
+
+int hufk_unpack_blank(const struct hufd_dec_item *items, uint32_t n_items, struct hufd_dec_item *packed, void *stream) {
+    if (n_items == 0) {
         return 0;
     }
-    const uint32_t tiles = hufk_pack_tiles(n_items, tile_items);
-    const u64 align_mask = align - 1;
-    if (tiles > 1) {
-        hipLaunchKernelGGL(
-            pack_tile_sums_kernel, dim3(tiles - 1), dim3(kPackThreads), kPackLdsBytes, (hipStream_t)stream, lengths, n_items, tile_items,
-            align_mask, tile_sums); /* (nobody reads the last tile's sums) */
+    hipLaunchKernelGGL(
+        unpack_records_kernel, dim3((n_items + kPackThreads - 1) / kPackThreads), dim3(kPackThreads), 0, (hipStream_t)stream, items, packed,
+        (const hufd_chunk_rec *)nullptr, (hufd_chunk_rec *)nullptr, n_items);
+    return (int)hipGetLastError();
+}
+
+int hufk_unpack_offsets(
+    const struct hufd_dec_item *items, const struct hufd_dec_result *counts, uint32_t n_items, uint32_t tile_items, uint64_t align,
+    uint64_t capacity, uint64_t *tile_sums, uint64_t *offsets, struct hufd_dec_item *packed, uint64_t *summary,
+    const struct hufd_chunk_rec *chunk_rec, uint32_t n_chunks, struct hufd_chunk_rec *packed_rec, void *stream) {
+    const int e = pack_offsets_launch(
+        items, counts, 1u, n_items, tile_items, align, capacity, tile_sums, offsets, packed, summary, (hipStream_t)stream);
+    if (e || n_items == 0 || n_chunks == 0) {
+        return e;
     }
     hipLaunchKernelGGL(
-        pack_offsets_kernel, dim3(tiles), dim3(kPackThreads), kPackLdsBytes, (hipStream_t)stream, items, lengths, n_items, tile_items,
-        align_mask, capacity, (const u64 *)tile_sums, offsets, packed, summary);
+        unpack_records_kernel, dim3((n_chunks + kPackThreads - 1) / kPackThreads), dim3(kPackThreads), 0, (hipStream_t)stream,
+        (const hufd_dec_item *)nullptr, packed, chunk_rec, packed_rec, n_chunks);
     return (int)hipGetLastError();
 }
 

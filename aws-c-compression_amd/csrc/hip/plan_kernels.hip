@@ -42,6 +42,7 @@ struct raw_item { /* either kind of item as its source has it */
     u32 bits;    /* decode: first_bit; encode: overflow bits */
     u32 pattern; /* encode: overflow pattern */
     u32 eos;     /* encode */
+    u32 bad;     /* the source itself says the item cannot be (offsets that decrease) */
 };
 
 template <bool ENC>
@@ -49,6 +50,7 @@ __device__ __forceinline__ raw_item load_item(const hufd_item_source &src, u32 i
     raw_item r;
     r.pattern = 0;
     r.eos = 0;
+    r.bad = 0;
     if (src.kind == HUFD_ITEMS_STRIDED) {
         r.in_off = src.in_offset + (u64)i * src.in_stride;
         r.in_len = src.in_len;
@@ -65,6 +67,21 @@ __device__ __forceinline__ raw_item load_item(const hufd_item_source &src, u32 i
         r.in_len = produced < e.out_cap ? produced : e.out_cap;
         r.out_off = e.in_off;
         r.out_cap = e.in_len;
+        r.bits = 0;
+    } else if (!ENC && src.kind == HUFD_ITEMS_PACKED_INPUT) {
+        /* item i of a packed buffer: from its offset to the next one, or as long as the sender says */
+        const u64 at = src.packed_offsets[i];
+        r.in_off = at;
+        if (src.packed_lengths) {
+            r.in_len = src.packed_lengths[i];
+            r.bad = i > 0 && src.packed_offsets[i - 1] > at;
+        } else {
+            const u64 next = src.packed_offsets[(u64)i + 1];
+            r.in_len = next >= at ? next - at : 0;
+            r.bad = next < at;
+        }
+        r.out_off = 0;
+        r.out_cap = 0;
         r.bits = 0;
     } else if (ENC) {
         const hufd_raw_enc_item e = reinterpret_cast<const hufd_raw_enc_item *>(src.raw)[i];
@@ -120,7 +137,7 @@ __global__ __launch_bounds__(kPlanThreads) void plan_stats_kernel(hufd_item_sour
         bits = r.bits > bits ? r.bits : bits;
         /* (an item is refused where the host's loop refuses it: a decode item holds less than 4 GiB; an encode item's
          *  segments must be a number the 32-bit counts below can hold -- more of them than that is no plan either way) */
-        invalid |= (ENC ? (r.bits > 32 || r.in_len > kEncItemMaxBytes) : (r.bits > 7 || r.in_len > 0xFFFFFFFFull)) ? 1u : 0u;
+        invalid |= (ENC ? (r.bits > 32 || r.in_len > kEncItemMaxBytes) : (r.bits > 7 || r.in_len > 0xFFFFFFFFull || r.bad)) ? 1u : 0u;
     }
 #pragma unroll
     for (u32 d = kWave / 2; d > 0; d >>= 1) {

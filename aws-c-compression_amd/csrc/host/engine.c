@@ -1524,6 +1524,8 @@ static int dec_plan_fill(
     /* a failed refill must not leave counts of the fill before behind (the device arrays may be gone or too small) */
     p->n_items = p->n_chunks = p->n_large = p->n_runs = p->n_tail = p->n_fixed = p->n_wide = 0;
     p->quiet = false; /* (other items: nothing is known of what their launches list) */
+    p->packed = p->packed_sized = false;
+    p->longest_in_len = 0;
     p->n_tiny = p->n_deep = 0;
     memset(&p->stats, 0, sizeof(p->stats));
     p->chained = false;
@@ -1566,6 +1568,7 @@ static int dec_plan_fill(
         p->n_tiny = (uint32_t)n_items;
         p->stats.items = p->stats.by_thread = n_items;
         p->stats.thread_limit = tiny_limit;
+        p->longest_in_len = stats.longest;
         return AWS_OP_SUCCESS;
     }
     uint64_t n_chunks = 0, n_large = 0, n_runs = 0, n_cut = 0;
@@ -1801,6 +1804,7 @@ static int dec_plan_fill(
         const bool packs = narrow >= HUFD_DEC_PACK_MIN_CHUNKS && p->tail_lanes + 2u <= HUFD_DEC_LANES / 2;
         p->stats.items = n_items;
         p->stats.thread_limit = tiny_limit;
+        p->longest_in_len = stats.longest;
         p->stats.by_thread = tiny;
         p->stats.by_blocks = n_wide + fixed_items;
         p->stats.by_wave = eng->tables.deep_entries ? 0 : deep;
@@ -1874,6 +1878,28 @@ static int dec_items_to_host(
         if (!e) {
             e = hufs_stream_sync(st);
         }
+    } else if (src->kind == HUFD_ITEMS_PACKED_INPUT) {
+        const size_t n_offsets = src->packed_lengths ? n_items : n_items + 1;
+        uint64_t *at = malloc((n_offsets ? n_offsets : 1) * sizeof(*at));
+        uint64_t *len = malloc((n_items ? n_items : 1) * sizeof(*len));
+        e = at && len ? 0 : 2;
+        if (!e && n_items) {
+            e = hufs_copy_d2h(at, src->packed_offsets, n_offsets * sizeof(*at), st);
+        }
+        if (!e && n_items && src->packed_lengths) {
+            e = hufs_copy_d2h(len, src->packed_lengths, n_items * sizeof(*len), st);
+        }
+        if (!e) {
+            e = hufs_stream_sync(st);
+        }
+        for (size_t i = 0; i < n_items && !e; ++i) {
+            /* (offsets that decrease: a length no plan takes, as the device planner's `invalid`) */
+            const bool bad = src->packed_lengths ? (i > 0 && at[i - 1] > at[i]) : at[i + 1] < at[i];
+            items[i].in_offset = at[i];
+            items[i].in_len = bad ? UINT64_MAX : (src->packed_lengths ? len[i] : at[i + 1] - at[i]);
+        }
+        free(at);
+        free(len);
     } else {
         struct hufd_enc_item *ei = malloc((n_items ? n_items : 1) * sizeof(*ei));
         struct hufd_enc_result *er = malloc((n_items ? n_items : 1) * sizeof(*er));
@@ -1925,6 +1951,8 @@ static int dec_plan_fill_on_device(struct aws_huffman_amd_decode_plan *p, const 
     }
     p->n_items = p->n_chunks = p->n_large = p->n_runs = p->n_tail = p->n_fixed = p->n_wide = 0;
     p->quiet = false; /* (other items: nothing is known of what their launches list) */
+    p->packed = p->packed_sized = false;
+    p->longest_in_len = 0;
     p->n_tiny = p->n_deep = 0;
     memset(&p->stats, 0, sizeof(p->stats));
     p->chained = false;
@@ -1980,6 +2008,7 @@ static int dec_plan_fill_on_device(struct aws_huffman_amd_decode_plan *p, const 
         const bool packs = narrow >= HUFD_DEC_PACK_MIN_CHUNKS && p->tail_lanes + 2u <= HUFD_DEC_LANES / 2;
         p->stats.items = n_items;
         p->stats.thread_limit = t.tiny_limit;
+        p->longest_in_len = t.longest;
         p->stats.by_thread = tiny;
         p->stats.by_wave = coop;
         p->stats.by_pieces = t.totals[7];
@@ -2031,6 +2060,7 @@ void aws_huffman_amd_decode_plan_destroy(struct aws_huffman_amd_decode_plan *p) 
         }
         ON_DEVICE(p->engine->device);
         dec_plan_release_device(p);
+        hufs_free(p->d_packed_arena);
         hufs_free(p->d_plan_scratch);
         hufs_event_destroy(p->done_event);
         hufs_free(p->d_wide_block);
@@ -2049,11 +2079,12 @@ int aws_huffman_amd_decode_plan_launch(
     return aws_huffman_amd_decode_plan_launch_staged(p, device_input, device_output, stream, NULL);
 }
 
-int aws_huffman_amd_decode_plan_launch_staged(
+/* what a launch of the plan hands the kernels */
+static void dec_plan_launch_args(
     struct aws_huffman_amd_decode_plan *p,
+    struct hufk_decode_args *args,
     const void *device_input,
     void *device_output,
-    void *stream,
     void **stage_events) {
 
     struct hufk_decode_args a;
@@ -2121,12 +2152,164 @@ int aws_huffman_amd_decode_plan_launch_staged(
         a.few_walks = road & AWS_HUFFMAN_AMD_TEST_DECODE_LONG_WAY ? 0u : 1u;
     }
     a.stage_events = stage_events;
+    *args = a;
+}
+
+int aws_huffman_amd_decode_plan_launch_staged(
+    struct aws_huffman_amd_decode_plan *p,
+    const void *device_input,
+    void *device_output,
+    void *stream,
+    void **stage_events) {
+
+    struct hufk_decode_args a;
+    dec_plan_launch_args(p, &a, device_input, device_output, stage_events);
+    p->packed = false; /* (the results are results for the plan's own capacities) */
     ON_DEVICE(p->engine->device);
     int err = hufk_decode_launch(&a, stream ? stream : p->engine->stream);
     if (!err) {
         err = plan_mark_done(&p->done_event, &p->done_on_engine_stream, p->engine, stream);
     }
     return err ? raise_hip(err) : AWS_OP_SUCCESS;
+}
+
+/* ------------------------------------------------------------------ packed decode launches (huffman_amd_packed.h) */
+
+/* as enc_plan_reserve_packed: the second record arrays, the scan's tile sums and its summary words (grown, never shrunk);
+ * an allocation, so not inside a graph capture -- the first packed launch of a plan, or of more items or chunks */
+static int dec_plan_reserve_packed(struct aws_huffman_amd_decode_plan *p, size_t n_items, size_t n_chunks, size_t n_tiles) {
+    if (p->d_packed_arena && n_items <= p->cap_packed_items && n_chunks <= p->cap_packed_chunks && n_tiles <= p->cap_pack_tiles) {
+        return 0;
+    }
+    hufs_free(p->d_packed_arena); /* (waits for what still reads it) */
+    p->d_packed_arena = NULL;
+    p->cap_packed_items = p->cap_packed_chunks = p->cap_pack_tiles = 0;
+    /* as many as the plan's own arrays: a reset within them allocates nothing */
+    const size_t ci = n_items > p->cap_items ? n_items : p->cap_items;
+    const size_t cc = n_chunks > p->cap_chunks ? n_chunks : p->cap_chunks;
+    size_t total = 0;
+    const size_t at_items = arena_cut(&total, ci * sizeof(struct hufd_dec_item));
+    const size_t at_chunks = arena_cut(&total, (cc ? cc : 1) * sizeof(struct hufd_chunk_rec));
+    const size_t at_sums = arena_cut(&total, 2 * n_tiles * sizeof(uint64_t));
+    const size_t at_summary = arena_cut(&total, 2 * sizeof(uint64_t));
+    p->d_packed_arena = hufs_malloc(total);
+    if (!p->d_packed_arena) {
+        return 2;
+    }
+    p->d_packed_items = (void *)((uint8_t *)p->d_packed_arena + at_items);
+    p->d_packed_chunk_rec = (void *)((uint8_t *)p->d_packed_arena + at_chunks);
+    p->d_pack_tile_sums = (void *)((uint8_t *)p->d_packed_arena + at_sums);
+    p->d_pack_summary = (void *)((uint8_t *)p->d_packed_arena + at_summary);
+    p->cap_packed_items = ci;
+    p->cap_packed_chunks = cc;
+    p->cap_pack_tiles = n_tiles;
+    return 0;
+}
+
+int aws_huffman_amd_decode_plan_launch_packed(
+    struct aws_huffman_amd_decode_plan *p,
+    const void *device_input,
+    void *device_output,
+    uint64_t output_capacity,
+    uint64_t *device_offsets,
+    uint32_t align,
+    void *stream) {
+
+    if (!p || !device_offsets || ((uintptr_t)device_offsets & 7u) || align == 0 || align > 4096 || (align & (align - 1)) ||
+        (!device_output && output_capacity)) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    void *st = stream ? stream : p->engine->stream;
+    if (p->n_items == 0) {
+        ON_DEVICE(p->engine->device);
+        const int e = hufs_memset(device_offsets, 0, sizeof(uint64_t), st);
+        if (e) {
+            return raise_hip(e);
+        }
+        p->packed = false;
+        p->packed_sized = true;
+        return AWS_OP_SUCCESS;
+    }
+    struct hufk_decode_pack pk;
+    memset(&pk, 0, sizeof(pk));
+    pk.tile_items = hufk_pack_tile_items(p->n_items, __atomic_load_n(&s_pack_tile_items, __ATOMIC_RELAXED));
+    ON_DEVICE(p->engine->device);
+    int err = dec_plan_reserve_packed(p, p->n_items, p->n_chunks, hufk_pack_tiles(p->n_items, pk.tile_items));
+    if (err) {
+        return raise_hip(err);
+    }
+    /* the most symbols a chunk that holds the end of a stream can decode to, + 32, as the plan's own number -- but that
+     * one is cut to the items' own capacities, which a packed launch does not use */
+    {
+        const uint64_t in_chunk = p->longest_in_len < HUFD_DEC_CHUNK_BYTES + 8u ? p->longest_in_len : HUFD_DEC_CHUNK_BYTES + 8u;
+        const uint32_t shortest = p->engine->tables.min_bits ? p->engine->tables.min_bits : 1u;
+        pk.tail_stage_bytes = p->longest_in_len ? (uint32_t)(in_chunk * 8 / shortest + 1 + 32) : 0u;
+    }
+    pk.align = align;
+    pk.capacity = output_capacity;
+    pk.tile_sums = p->d_pack_tile_sums;
+    pk.offsets = device_offsets;
+    pk.summary = p->d_pack_summary;
+    pk.items = p->d_packed_items;
+    pk.chunk_rec = p->d_packed_chunk_rec;
+    struct hufk_decode_args a;
+    dec_plan_launch_args(p, &a, device_input, device_output, NULL);
+    err = hufk_decode_launch_packed(&a, &pk, st);
+    if (!err) {
+        err = plan_mark_done(&p->done_event, &p->done_on_engine_stream, p->engine, stream);
+    }
+    if (err) {
+        return raise_hip(err);
+    }
+    p->packed = true;
+    p->packed_sized = true;
+    return AWS_OP_SUCCESS;
+}
+
+int aws_huffman_amd_decode_plan_packed_size(
+    struct aws_huffman_amd_decode_plan *p,
+    uint64_t *total_symbols,
+    uint64_t *longest_item_symbols,
+    void *stream) {
+
+    if (!p || !p->packed_sized) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    uint64_t summary[2] = {0, 0};
+    ON_DEVICE(p->engine->device);
+    void *st = stream ? stream : p->engine->stream;
+    int err = p->n_items ? hufs_copy_d2h(summary, p->d_pack_summary, sizeof(summary), st) : 0;
+    if (!err) {
+        err = hufs_stream_sync(st);
+    }
+    if (err) {
+        return raise_hip(err);
+    }
+    if (total_symbols) {
+        *total_symbols = summary[0];
+    }
+    if (longest_item_symbols) {
+        *longest_item_symbols = summary[1];
+    }
+    return AWS_OP_SUCCESS;
+}
+
+int aws_huffman_amd_decode_plan_reset_packed_input(
+    struct aws_huffman_amd_decode_plan *p,
+    const uint64_t *device_offsets,
+    const uint64_t *device_lengths,
+    size_t item_count,
+    void *stream) {
+
+    if (!p || (!device_offsets && item_count) || ((uintptr_t)device_offsets & 7u) || ((uintptr_t)device_lengths & 7u)) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    struct hufd_item_source src;
+    memset(&src, 0, sizeof(src));
+    src.kind = HUFD_ITEMS_PACKED_INPUT;
+    src.packed_offsets = device_offsets;
+    src.packed_lengths = device_lengths;
+    return dec_plan_fill_on_device(p, &src, item_count, stream);
 }
 
 /*
@@ -2206,10 +2389,12 @@ int aws_huffman_amd_decode_plan_results(
         p->quiet = !(listed[HUFK_DEC_COUNT_SLOW] | listed[HUFK_DEC_COUNT_LONG] | listed[HUFK_DEC_COUNT_FEW] |
                      listed[HUFK_DEC_COUNT_EMIT] | listed[HUFK_DEC_COUNT_DENSE]);
     }
-    if (p->chained) {
-        /* the items' lengths were never on the host: the device's records say what each result is a result of */
+    if (p->chained || p->packed) {
+        /* the items' lengths were never on the host: the device's records say what each result is a result of (after a
+         * packed launch the records that launch wrote: the room it gave each item) */
+        const struct hufd_dec_item *records = p->packed ? p->d_packed_items : p->d_items;
         struct hufd_dec_item *dev_items = malloc((p->n_items ? p->n_items : 1) * sizeof(*dev_items));
-        err = dev_items ? hufs_copy_d2h(dev_items, p->d_items, (size_t)p->n_items * sizeof(*dev_items), st) : 2;
+        err = dev_items ? hufs_copy_d2h(dev_items, records, (size_t)p->n_items * sizeof(*dev_items), st) : 2;
         if (!err) {
             err = hufs_stream_sync(st);
         }
@@ -2275,6 +2460,8 @@ int aws_huffman_amd_decode_plan_from_encode(
     }
     p->n_items = p->n_chunks = p->n_large = p->n_runs = p->n_tail = p->n_fixed = p->n_wide = 0;
     p->quiet = false; /* (other items: nothing is known of what their launches list) */
+    p->packed = p->packed_sized = false;
+    p->longest_in_len = 0;
     p->n_tiny = p->n_deep = 0;
     memset(&p->stats, 0, sizeof(p->stats));
     p->chained = false;

@@ -165,6 +165,20 @@ struct aws_huffman_amd_decode_plan {
     uint32_t *d_fixed;
     uint32_t n_fixed;
     size_t cap_fixed;
+    /* packed launches (huffman_amd_packed.h), as in an encode plan: a second array of item records and one of chunk
+     * records -- the plan's own with out_off / out_cap rewritten by hufk_unpack_offsets --, the scan's tile sums and its
+     * two summary words; ONE allocation, made by the first packed launch and grown by a later one of more items, chunks
+     * or tiles */
+    void *d_packed_arena;
+    struct hufd_dec_item *d_packed_items;      /* [cap_packed_items] */
+    struct hufd_chunk_rec *d_packed_chunk_rec; /* [cap_packed_chunks] */
+    uint64_t *d_pack_tile_sums;                /* [2 * cap_pack_tiles] */
+    uint64_t *d_pack_summary;                  /* [2]: the total, the largest reserved length */
+    size_t cap_packed_items, cap_packed_chunks, cap_pack_tiles;
+    uint64_t longest_in_len; /* encoded bytes of the longest item (0: not known): bounds what a chunk can decode to when the
+                              * items' own capacities do not */
+    bool packed;       /* the last launch was a packed one: its results are results for the room d_packed_items say */
+    bool packed_sized; /* ... and one was made since the plan was filled: d_pack_summary is of these items */
 };
 
 /* the engine cache of huffman.c: what an engine is recognised by besides the coder's address, and the two ways out of it */

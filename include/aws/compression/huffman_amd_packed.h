@@ -68,6 +68,76 @@ int aws_huffman_amd_encode_plan_packed_size(
     uint64_t *longest_item_bytes,
     void *stream);
 
+/*
+ * Packed batch decode: the mirror.  A receiver of a packed buffer and its offsets -- from a file, a socket, another GPU --
+ * does not know how many symbols an item decodes to; the device finds out and lays the output out itself:
+ *
+ *   aws_huffman_amd_decode_plan_reset_packed_input(plan, d_in_offsets, NULL, item_count, stream);
+ *   aws_huffman_amd_decode_plan_launch_packed(plan, d_input, NULL, 0, d_out_offsets, 1, stream);     (a size query, or
+ *   aws_huffman_amd_decode_plan_packed_size(plan, &total, &longest, stream);                          guess a capacity)
+ *   aws_huffman_amd_decode_plan_launch_packed(plan, d_input, d_output, total, d_out_offsets, 1, stream);
+ *
+ * Decodes the plan's items back to back into device_output.  With sym_i = the symbols aws_huffman_decode writes for item
+ * i when it never runs out of room (the reference's aws_huffman_decoder_allow_growth: the walk from the item's first_bit
+ * to the end of the stream, a code that runs past it, or a window without a code; symbols the padding bits spell count):
+ *   offsets[0] = 0,  offsets[i + 1] = round_up(offsets[i] + sym_i, align)
+ * always written in full, never clipped: device_offsets[item_count] is what output_capacity had to be.
+ * An item whose symbols [offsets[i], offsets[i] + sym_i) all lie in front of output_capacity is aws_huffman_decode into a
+ * byte_buf of capacity sym_i at device_output + offsets[i]: success with produced = sym_i, or
+ * AWS_ERROR_COMPRESSION_UNKNOWN_SYMBOL.  Any other item gets capacity 0 -- there is no partial room: a caller who ran
+ * short allocates device_offsets[item_count] and launches again --: AWS_ERROR_SHORT_BUFFER with produced 0 and
+ * bits_consumed 0 where sym_i > 0, the reference's answer for capacity 0 where sym_i = 0.  Nothing at or behind
+ * device_output + output_capacity and nothing in the gaps an alignment leaves is written.  The items' own out_offset /
+ * out_capacity are neither read nor changed (a later aws_huffman_amd_decode_plan_launch behaves as before).
+ * aws_huffman_amd_decode_plan_results after this launch reports against the capacity the launch gave each item.
+ *
+ * device_output NULL with output_capacity 0 is a size query: the offsets only.
+ * Asynchronous on `stream`, no host wait; device_offsets, align, the plan's first packed launch (it allocates, so it
+ * cannot be inside a graph capture; later ones can), the empty plan and AWS_ERROR_INVALID_ARGUMENT: as for
+ * aws_huffman_amd_encode_plan_launch_packed.
+ * The encoded bytes are walked once; only items short enough for a thread or a wave each (and those of a coder with codes
+ * of more than 12 bits or of one length) are walked twice, once to count.
+ */
+AWS_COMPRESSION_API
+int aws_huffman_amd_decode_plan_launch_packed(
+    struct aws_huffman_amd_decode_plan *plan,
+    const void *device_input,
+    void *device_output,
+    uint64_t output_capacity,
+    uint64_t *device_offsets,
+    uint32_t align,
+    void *stream);
+
+/*
+ * Waits for the plan's last packed launch (made on `stream`).  *total_symbols = device_offsets[item_count];
+ * *longest_item_symbols = the largest reserved length (sym_i rounded up to the alignment) of one item.  Either pointer
+ * may be NULL.  AWS_ERROR_INVALID_ARGUMENT: no packed launch since the plan was made or reset.
+ */
+AWS_COMPRESSION_API
+int aws_huffman_amd_decode_plan_packed_size(
+    struct aws_huffman_amd_decode_plan *plan,
+    uint64_t *total_symbols,
+    uint64_t *longest_item_symbols,
+    void *stream);
+
+/*
+ * Makes the plan, on the device, from a packed input layout: item i reads device_lengths[i] bytes at device_offsets[i],
+ * from bit 0.  device_lengths NULL: device_offsets[i + 1] - device_offsets[i] bytes (device_offsets then holds
+ * item_count + 1 numbers: what aws_huffman_amd_encode_plan_launch_packed wrote with align 1; with a larger alignment the
+ * gap bytes were never written, so the sender ships the lengths, and device_offsets holds item_count numbers).
+ * The items' own out_offset and out_capacity are 0: such a plan is meant for packed launches, and a plain launch of it
+ * reports AWS_ERROR_SHORT_BUFFER for every item that holds a symbol.
+ * Offsets that decrease, or an item of 4 GiB or more: AWS_ERROR_INVALID_ARGUMENT and a plan without items.  Everything
+ * else as aws_huffman_amd_decode_plan_reset_device_items (uint64_t arrays in device memory, 8-byte aligned).
+ */
+AWS_COMPRESSION_API
+int aws_huffman_amd_decode_plan_reset_packed_input(
+    struct aws_huffman_amd_decode_plan *plan,
+    const uint64_t *device_offsets,
+    const uint64_t *device_lengths,
+    size_t item_count,
+    void *stream);
+
 /* testing: the items one workgroup of the offset scan takes (any number >= 1: a small batch then crosses many tile
  * boundaries); 0: back to the built-in rule (1024, more for batches of many millions) */
 AWS_COMPRESSION_API
