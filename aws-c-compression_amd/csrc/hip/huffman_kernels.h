@@ -240,6 +240,17 @@ int hufk_unpack_offsets(
     const struct hufd_dec_item *items, const struct hufd_dec_result *counts, uint32_t n_items, uint32_t tile_items, uint64_t align,
     uint64_t capacity, uint64_t *tile_sums, uint64_t *offsets, struct hufd_dec_item *packed, uint64_t *summary,
     const struct hufd_chunk_rec *chunk_rec, uint32_t n_chunks, struct hufd_chunk_rec *packed_rec, void *stream);
+/* A coder fitted on the device (fit_kernels.hip, huffman_amd_fit.h): ONE launch of one workgroup writes enc_table[256] and
+ * dec_lut[1 << max_bits] -- from 256 counts (from_lengths 0: package-merge lengths in min_bits .. max_bits for all 256
+ * symbols, also left in num_bits_out where that is not NULL), or from 256 lengths (from_lengths 1) -- and *status (NULL: not
+ * wanted): 0, or why the tables were left as they were.  4 <= min_bits <= 8 <= max_bits <= 12, min_bits < max_bits. */
+#define HUFK_FIT_COUNTS_TOO_LARGE 1u     /* counts that sum to 2^58 or more */
+#define HUFK_FIT_LENGTH_ZERO 2u          /* a symbol without a code */
+#define HUFK_FIT_LENGTH_OUT_OF_BOUNDS 3u /* a length outside min_bits .. max_bits */
+#define HUFK_FIT_KRAFT_ABOVE_ONE 4u      /* not a prefix code */
+int hufk_fit_tables(
+    uint32_t from_lengths, const uint64_t *counts, const uint8_t *lengths, uint32_t min_bits, uint32_t max_bits, uint64_t *enc_table,
+    uint16_t *dec_lut, uint8_t *num_bits_out, uint32_t *status, void *stream);
 
 #ifdef __cplusplus
 }

@@ -105,8 +105,9 @@ __device__ __forceinline__ raw_item load_item(const hufd_item_source &src, u32 i
 
 /* ------------------------------------------------------------------ pass 1: what the thread-per-item rule asks */
 
-template <bool ENC>
-__global__ __launch_bounds__(kPlanThreads) void plan_stats_kernel(hufd_item_source src, u32 n_items, u64 class0, u64 class1, plan_stats *stats) {
+/* (one kernel for both kinds of item, `enc` a launch argument: a thread's bookkeeping per item, nothing a second build
+ * of it would make faster) */
+__global__ __launch_bounds__(kPlanThreads) void plan_stats_kernel(hufd_item_source src, u32 enc, u32 n_items, u64 class0, u64 class1, plan_stats *stats) {
     plan_stats *local = reinterpret_cast<plan_stats *>(dyn_lds);
     if (threadIdx.x == 0) {
         plan_stats z;
@@ -123,7 +124,7 @@ __global__ __launch_bounds__(kPlanThreads) void plan_stats_kernel(hufd_item_sour
      * memory line -- from a workgroup per 256 items those were 37 000 of them for a million items, one after the other at
      * the memory side: 0.39 ms, the whole of the pass; from at most kPlanStatsBlocks workgroups 1 200) */
     for (u64 at = i; at < n_items; at += (u64)gridDim.x * kPlanThreads) {
-        const raw_item r = load_item<ENC>(src, (u32)at);
+        const raw_item r = enc ? load_item<true>(src, (u32)at) : load_item<false>(src, (u32)at);
         const u64 classes[2] = {class0, class1};
         for (u32 c = 0; c < 2; ++c) {
             if (r.in_len <= classes[c]) {
@@ -137,7 +138,7 @@ __global__ __launch_bounds__(kPlanThreads) void plan_stats_kernel(hufd_item_sour
         bits = r.bits > bits ? r.bits : bits;
         /* (an item is refused where the host's loop refuses it: a decode item holds less than 4 GiB; an encode item's
          *  segments must be a number the 32-bit counts below can hold -- more of them than that is no plan either way) */
-        invalid |= (ENC ? (r.bits > 32 || r.in_len > kEncItemMaxBytes) : (r.bits > 7 || r.in_len > 0xFFFFFFFFull || r.bad)) ? 1u : 0u;
+        invalid |= (enc ? (r.bits > 32 || r.in_len > kEncItemMaxBytes) : (r.bits > 7 || r.in_len > 0xFFFFFFFFull || r.bad)) ? 1u : 0u;
     }
 #pragma unroll
     for (u32 d = kWave / 2; d > 0; d >>= 1) {
@@ -575,8 +576,8 @@ int plan_count(
         return (int)e;
     }
     hipLaunchKernelGGL(
-        (plan_stats_kernel<ENC>), dim3(blocks < kPlanStatsBlocks ? blocks : kPlanStatsBlocks), dim3(kPlanThreads), sizeof(plan_stats), st, *src,
-        n_items, class0, class1, stats);
+        plan_stats_kernel, dim3(blocks < kPlanStatsBlocks ? blocks : kPlanStatsBlocks), dim3(kPlanThreads), sizeof(plan_stats), st, *src,
+        ENC ? 1u : 0u, n_items, class0, class1, stats);
     hipLaunchKernelGGL(plan_decide_kernel, dim3(1), dim3(64), 0, st, stats, class0, class1, per_byte, decision);
     hipLaunchKernelGGL((plan_count_kernel<ENC>), dim3(blocks), dim3(kPlanThreads), 128, st, *src, n_items, decision, shortest_code, solo_limit, stats, block_sums);
     hipLaunchKernelGGL(plan_scan_blocks_kernel, dim3(1), dim3(kPlanThreads), 128, st, block_sums, blocks, decision);

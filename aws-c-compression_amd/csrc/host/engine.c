@@ -8,8 +8,10 @@
 #include "engine.h"
 
 #include <aws/compression/huffman_amd_build.h>
+#include <aws/compression/huffman_amd_fit.h>
 #include <aws/compression/huffman_amd_packed.h>
 
+#include <assert.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -252,6 +254,25 @@ static int deep_table_build(struct aws_huffman_amd_engine *eng, struct aws_huffm
     return AWS_OP_SUCCESS;
 }
 
+/* the engine's own stream, and the second stream with its two events; 0 or a HIP error */
+static int engine_streams_create(struct aws_huffman_amd_engine *eng) {
+    const int err = hufs_stream_create(&eng->stream);
+    if (!err && hufs_stream_create(&eng->side_stream) == 0) {
+        eng->fork_event = hufs_event_create_untimed();
+        eng->join_event = hufs_event_create_untimed();
+        if (!eng->fork_event || !eng->join_event) {
+            /* (no overlap then: the kernels run one after the other on the one stream) */
+            hufs_event_destroy(eng->fork_event);
+            hufs_event_destroy(eng->join_event);
+            hufs_stream_destroy(eng->side_stream);
+            eng->fork_event = eng->join_event = eng->side_stream = NULL;
+        }
+    } else {
+        eng->side_stream = NULL;
+    }
+    return err;
+}
+
 int aws_huffman_amd_engine_new(
     struct aws_huffman_amd_engine **out_engine,
     struct aws_huffman_symbol_coder *coder,
@@ -431,20 +452,7 @@ int aws_huffman_amd_engine_new(
         eng->tables.min_bits = 1;
     }
 
-    int err = hufs_stream_create(&eng->stream);
-    if (!err && hufs_stream_create(&eng->side_stream) == 0) {
-        eng->fork_event = hufs_event_create_untimed();
-        eng->join_event = hufs_event_create_untimed();
-        if (!eng->fork_event || !eng->join_event) {
-            /* (no overlap then: the kernels run one after the other on the one stream) */
-            hufs_event_destroy(eng->fork_event);
-            hufs_event_destroy(eng->join_event);
-            hufs_stream_destroy(eng->side_stream);
-            eng->fork_event = eng->join_event = eng->side_stream = NULL;
-        }
-    } else {
-        eng->side_stream = NULL;
-    }
+    int err = engine_streams_create(eng);
     if (!err && eng->deep_lut_host) {
         eng->d_deep_lut =
             device_upload(eng->deep_lut_host, (size_t)eng->tables.deep_entries * sizeof(uint32_t), eng->stream, &err);
@@ -531,6 +539,132 @@ bool aws_huffman_amd_engine_can_decode(const struct aws_huffman_amd_engine *eng)
 
 void *aws_huffman_amd_engine_stream(struct aws_huffman_amd_engine *eng) {
     return eng->stream;
+}
+
+/* ------------------------------------------------------------------ engines fitted on the device (huffman_amd_fit.h) */
+
+_Static_assert(AWS_HUFFMAN_AMD_FIT_COUNTS_TOO_LARGE == HUFK_FIT_COUNTS_TOO_LARGE, "fit status");
+_Static_assert(AWS_HUFFMAN_AMD_FIT_LENGTH_ZERO == HUFK_FIT_LENGTH_ZERO, "fit status");
+_Static_assert(AWS_HUFFMAN_AMD_FIT_LENGTH_OUT_OF_BOUNDS == HUFK_FIT_LENGTH_OUT_OF_BOUNDS, "fit status");
+_Static_assert(AWS_HUFFMAN_AMD_FIT_KRAFT_ABOVE_ONE == HUFK_FIT_KRAFT_ABOVE_ONE, "fit status");
+
+int aws_huffman_amd_engine_new_fitted(struct aws_huffman_amd_engine **out_engine, int device, uint32_t min_bits, uint32_t max_bits) {
+    /* (the caller's pointer is written on success only) */
+    if (!out_engine || min_bits < 4 || min_bits > 8 || max_bits < 8 || max_bits > HUFD_DEC_MAX_LUT_BITS || min_bits >= max_bits) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    if (hufs_device_count() <= 0) {
+        return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION); /* no GPU: there is no CPU path */
+    }
+    if (device < 0 && hufs_get_device(&device)) {
+        return aws_raise_error(AWS_ERROR_UNKNOWN);
+    }
+    if (device >= hufs_device_count()) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    ON_DEVICE(device);
+    {
+        const int e = hufk_init();
+        if (e) {
+            return raise_hip(e);
+        }
+    }
+    struct aws_huffman_amd_engine *eng = calloc(1, sizeof(*eng));
+    if (!eng) {
+        return aws_raise_error(AWS_ERROR_OOM);
+    }
+    pthread_mutex_init(&eng->one_lock, NULL);
+    pthread_mutex_init(&eng->spare_lock, NULL);
+    eng->device = device;
+    eng->fitted = true;
+    /* no coder, no key: huffman.c's cache never holds such an engine.  Every decision the host makes from a coder reads
+     * one of these bounds (row_walk's certain steps, image and stage sizes, the one-pass rule, the capacity sums), and a
+     * fit keeps within them: plans made before a fit stay good behind it */
+    eng->can_encode = eng->can_decode = true;
+    eng->tables.enc_min_bits = eng->tables.min_bits = min_bits;
+    eng->tables.enc_max_bits = eng->tables.max_bits = eng->tables.lut_bits = max_bits;
+    eng->tables.n_states = max_bits > 8 ? max_bits : 8;
+    eng->tables.all_coded = 1;
+    {
+        const uint32_t road = testing_encode_road();
+        eng->single_pass = !(road & AWS_HUFFMAN_AMD_TEST_ENCODE_THREE_KERNEL);
+        eng->encode_fails = (road & AWS_HUFFMAN_AMD_TEST_ENCODE_ONE_PASS_FAILS) != 0;
+    }
+    int err = engine_streams_create(eng);
+    if (!err) {
+        eng->d_enc_table = hufs_malloc(256 * sizeof(uint64_t));
+        eng->d_dec_lut = hufs_malloc((size_t)sizeof(uint16_t) << max_bits);
+        err = eng->d_enc_table && eng->d_dec_lut ? 0 : 2;
+    }
+    if (err) {
+        aws_huffman_amd_engine_destroy(eng);
+        return raise_hip(err);
+    }
+    eng->tables.enc_table = eng->d_enc_table;
+    eng->tables.dec_lut = eng->d_dec_lut;
+    *out_engine = eng;
+    return AWS_OP_SUCCESS;
+}
+
+bool aws_huffman_amd_engine_is_fitted(const struct aws_huffman_amd_engine *eng) {
+    return eng && eng->fitted;
+}
+
+static int engine_fit(
+    struct aws_huffman_amd_engine *eng, const uint64_t *device_counts, const uint8_t *device_lengths, uint8_t *device_num_bits,
+    uint32_t *device_status, void *stream) {
+    const uint32_t lo = eng->tables.min_bits, hi = eng->tables.max_bits;
+    /* what the selection of the kernel (and of coder_build.c) stands on: X = 256 - 2^lo symbols too many for lo bits
+     * (none at 8), and the 2 X items it takes of the first list are there -- that list has 512 - 2^(9 - D) items */
+    assert(lo >= 4 && lo <= 8 && hi >= 8 && hi <= 12 && lo < hi);
+    assert(lo == 8 || 2u * (256u - (1u << lo)) <= 512u - (512u >> (hi - lo)));
+    ON_DEVICE(eng->device);
+    const int err = hufk_fit_tables(
+        device_lengths != NULL, device_counts, device_lengths, lo, hi, eng->d_enc_table, eng->d_dec_lut, device_num_bits, device_status,
+        stream ? stream : eng->stream);
+    if (err) {
+        return raise_hip(err);
+    }
+    eng->fit_enqueued = true;
+    return AWS_OP_SUCCESS;
+}
+
+int aws_huffman_amd_engine_fit_counts(
+    struct aws_huffman_amd_engine *eng, const uint64_t *device_counts, uint8_t *device_num_bits, uint32_t *device_status, void *stream) {
+    if (!eng || !eng->fitted || !device_counts || ((uintptr_t)device_counts & 7u) || ((uintptr_t)device_status & 3u)) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    return engine_fit(eng, device_counts, NULL, device_num_bits, device_status, stream);
+}
+
+int aws_huffman_amd_engine_fit_lengths(
+    struct aws_huffman_amd_engine *eng, const uint8_t *device_num_bits, uint32_t *device_status, void *stream) {
+    if (!eng || !eng->fitted || !device_num_bits || ((uintptr_t)device_status & 3u)) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    return engine_fit(eng, NULL, device_num_bits, NULL, device_status, stream);
+}
+
+int aws_huffman_amd_testing_engine_tables(
+    struct aws_huffman_amd_engine *eng, uint64_t enc_table[256], uint16_t *dec_lut, size_t dec_lut_entries) {
+    if (!eng || !enc_table || !dec_lut || !eng->d_enc_table || !eng->d_dec_lut ||
+        dec_lut_entries != (size_t)1 << eng->tables.lut_bits) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    ON_DEVICE(eng->device);
+    int err = hufs_copy_d2h(enc_table, eng->d_enc_table, 256 * sizeof(uint64_t), eng->stream);
+    if (!err) {
+        err = hufs_copy_d2h(dec_lut, eng->d_dec_lut, dec_lut_entries * sizeof(uint16_t), eng->stream);
+    }
+    if (!err) {
+        err = hufs_stream_sync(eng->stream);
+    }
+    return err ? raise_hip(err) : AWS_OP_SUCCESS;
+}
+
+/* a plan of an engine whose tables nobody has written yet is not launched */
+static bool engine_never_fitted(const struct aws_huffman_amd_engine *eng) {
+    return eng->fitted && !eng->fit_enqueued;
 }
 
 /* ------------------------------------------------------------------ encode plans */
@@ -1131,6 +1265,9 @@ int aws_huffman_amd_encode_plan_launch_staged(
     bool length_only,
     void *stream,
     void **stage_events) {
+    if (engine_never_fitted(p->engine)) {
+        return aws_raise_error(AWS_ERROR_INVALID_STATE);
+    }
     if (!length_only) {
         p->packed = false; /* (the output lies where the plan's own records say) */
     }
@@ -1183,6 +1320,9 @@ int aws_huffman_amd_encode_plan_launch_packed(
     if (!p || !device_offsets || ((uintptr_t)device_offsets & 7u) || align == 0 || align > 4096 || (align & (align - 1)) ||
         (!device_output && output_capacity)) {
         return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    if (engine_never_fitted(p->engine)) {
+        return aws_raise_error(AWS_ERROR_INVALID_STATE);
     }
     void *st = stream ? stream : p->engine->stream;
     if (p->n_items == 0) {
@@ -2162,6 +2302,9 @@ int aws_huffman_amd_decode_plan_launch_staged(
     void *stream,
     void **stage_events) {
 
+    if (engine_never_fitted(p->engine)) {
+        return aws_raise_error(AWS_ERROR_INVALID_STATE);
+    }
     struct hufk_decode_args a;
     dec_plan_launch_args(p, &a, device_input, device_output, stage_events);
     p->packed = false; /* (the results are results for the plan's own capacities) */
@@ -2218,6 +2361,9 @@ int aws_huffman_amd_decode_plan_launch_packed(
     if (!p || !device_offsets || ((uintptr_t)device_offsets & 7u) || align == 0 || align > 4096 || (align & (align - 1)) ||
         (!device_output && output_capacity)) {
         return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    if (engine_never_fitted(p->engine)) {
+        return aws_raise_error(AWS_ERROR_INVALID_STATE);
     }
     void *st = stream ? stream : p->engine->stream;
     if (p->n_items == 0) {

@@ -36,6 +36,10 @@ struct aws_huffman_amd_engine {
     struct hufd_tables tables;
     bool single_pass; /* enc_onepass where the coder allows it (the tests can make an engine that keeps to count / scan / pack) */
     bool encode_fails; /* a wave of enc_onepass is made to give up (tests of the way back: aws_huffman_amd_testing_set_encode_road) */
+    /* an engine without a coder (aws_huffman_amd_engine_new_fitted, huffman_amd_fit.h): `tables` holds the bounds declared
+     * when it was made, and the two device tables are written by fit_kernel; no host copy of them exists */
+    bool fitted;
+    bool fit_enqueued; /* ... and a fit has been enqueued at least once: plans may be launched */
 
     /* scratch of the host-pointer API: one item at a time, one caller at a time (`one_lock`); `users` keeps the
      * engine cache of huffman.c from retiring an engine somebody is inside of */

@@ -80,7 +80,9 @@ struct aws_huffman_amd_decode_result {
  * An engine (its plans included) is one host thread's at a time: launches of one
  * engine's plans are made one after the other -- they share the engine's second
  * stream and its events.  Threads that work side by side take an engine each
- * (aws_huffman_amd_shards does that per device).
+ * (aws_huffman_amd_shards does that per device).  An engine whose tables are made on
+ * the device (huffman_amd_fit.h) adds the same rule on the device's side: a fit and the
+ * launches that use or precede it are the caller's to order, on one stream or with events.
  */
 AWS_COMPRESSION_API
 int aws_huffman_amd_engine_new(
