@@ -45,6 +45,9 @@ AWS_EXTERN_C_BEGIN
 /*
  * An engine without a coder.  Its tables are made on the device, for codes of min_bits .. max_bits for all 256 symbols.
  * Bounds: 4 <= min_bits <= 8 <= max_bits <= 12, and min_bits < max_bits.  device -1 = current.
+ * With min_bits == 8 or max_bits == 8 a fit from counts can only ever yield the flat code of 8 bits a symbol (Kraft, 256
+ * coded symbols: none may be shorter than 8 under max_bits 8, none need be longer over min_bits 8): such an engine is
+ * accepted, and never compresses.  Bounds that leave the fit a choice have min_bits < 8 < max_bits.
  * Until a fit has been enqueued, launches of its plans raise AWS_ERROR_INVALID_STATE.
  * AWS_ERROR_INVALID_ARGUMENT: bounds outside the range, a NULL pointer, a device that does not exist;
  * AWS_ERROR_UNSUPPORTED_OPERATION without a GPU.  *engine is written on success only.

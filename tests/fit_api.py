@@ -1,8 +1,10 @@
 """ctypes face of include/aws/compression/huffman_amd_fit.h (coders fitted on the device) and what its tests share: the
 count vectors, the host's lengths and the tables written out in Python from the canonical rows, one check of a fit against
 both, and the oracle's coder of a fit.  Used by tests/test_emulated_fit.py (emulator build) and tests/test_gpu_fit.py
-(MI355X).  Nothing here asks a second engine what a table should hold."""
+(MI355X): every run_* scenario below is called by both, at the same sizes.  Nothing here asks a second engine what a table
+should hold."""
 import ctypes as C
+import types
 
 import numpy as np
 
@@ -10,11 +12,22 @@ import build_api as ba
 import harness
 import packed_api as pa
 import packed_decode_api as pda
+import parity_cases as pc
 
 AWS_ERROR_INVALID_STATE = 38
 FIT_OK, FIT_COUNTS_TOO_LARGE, FIT_LENGTH_ZERO, FIT_LENGTH_OUT_OF_BOUNDS, FIT_KRAFT_ABOVE_ONE = 0, 1, 2, 3, 4
-BOUNDS = [(4, 12), (4, 10), (5, 9), (7, 8), (4, 8), (8, 12)]
-ROAD_ONE_PASS = 1
+# (min_bits, max_bits) of the engines under test.  256 coded symbols and Kraft: with max_bits == 8 no length may be shorter
+# than 8, with min_bits == 8 the optimal code has none longer, so a fit from counts within (7, 8), (4, 8) or (8, 12) can
+# only ever yield the flat 8-bit code; the others have max_bits 9, 10, 11 and 12 with room for a spread of lengths
+BOUNDS = [(4, 12), (4, 10), (5, 9), (7, 8), (4, 8), (8, 12), (4, 9), (7, 9), (4, 11), (6, 11), (7, 12)]
+ROAD_ONE_PASS = pc.ROAD_ONE_PASS
+ROAD_OF = {None: pc.ROAD_ONE_PASS, "three-kernel": pc.ROAD_TWO_PASS, "one-pass-fails": pc.ROAD_GAVE_UP}
+INVALID = (-1, harness.AWS_ERROR_INVALID_ARGUMENT)
+
+
+def only_flat(lo, hi):
+    """Bounds under which every fit from counts is the flat 8-bit code."""
+    return lo == 8 or hi == 8
 
 
 def bind(lib):
@@ -221,6 +234,120 @@ def run_tables_equal_host(lib, engines):
             check_fit(lib, eng, counts, label)
 
 
+def run_fit_lengths(lib, first):
+    """test_fit_lengths: `first` is a (4, 12) engine.  A receiver fitted from the sender's 256 bytes in device memory has
+    the sender's tables; four refusals leave both tables as they were; a Kraft sum below 1 is taken and leaves the windows
+    nobody owns 0; a length the engine did not declare is refused."""
+    assert (first.lo, first.hi) == (4, 12)
+    lengths = check_fit(lib, first, printable_counts(), "printable")
+    enc, lut = first.tables()
+    second = FittedEngine(lib, 4, 12)
+    narrow = FittedEngine(lib, 4, 10)
+    try:
+        # the receiver's half, from the first engine's own 256 bytes in device memory
+        second.fill(second.d_status, 0xEE, 4)
+        assert second.fit_lengths_async(first.d_bits) == (0, 0)
+        assert second.status() == FIT_OK
+        enc2, lut2 = second.tables()
+        assert np.array_equal(enc, enc2) and np.array_equal(lut, lut2)
+        # refused, the tables as they were
+        for bad, why in (([0] + lengths[1:], FIT_LENGTH_ZERO), ([3] + lengths[1:], FIT_LENGTH_OUT_OF_BOUNDS),
+                         (lengths[:200] + [13] + lengths[201:], FIT_LENGTH_OUT_OF_BOUNDS), ([7] * 256, FIT_KRAFT_ABOVE_ONE)):
+            assert second.fit_lengths(bad) == why, (bad[:4], why)
+            enc2, lut2 = second.tables()
+            assert np.array_equal(enc, enc2) and np.array_equal(lut, lut2), why
+        # Kraft below 1: accepted, and the windows nobody owns say "no code" -- here one pair of 10-bit windows, behind
+        # the 9-bit code
+        short = [8] * 255 + [9]
+        assert narrow.fit_lengths(short) == FIT_OK
+        enc3, lut3 = narrow.tables()
+        want_enc, want_lut = expected_tables(host_rows(lib, short), 10)
+        assert np.array_equal(enc3, want_enc) and np.array_equal(lut3, want_lut)
+        assert list(np.flatnonzero(lut3 == 0)) == [1022, 1023]
+        # a length the (4, 10) engine did not declare
+        assert narrow.fit_lengths([8] * 254 + [7, 11]) == FIT_LENGTH_OUT_OF_BOUNDS
+        assert np.array_equal(narrow.tables()[1], want_lut)
+    finally:
+        second.close()
+        narrow.close()
+
+
+def run_interface_errors(lib):
+    """test_interface_errors: bounds, devices and pointers aws_huffman_amd_engine_new_fitted refuses (the caller's pointer
+    as it was); NULL and plain-engine arguments of the fits; the never-fitted state -- plans are made, no launch is taken,
+    nothing is written -- and the same plans taken behind the first fit; the optional status and lengths."""
+    h = C.c_void_p(0x1234)
+    for lo, hi in ((3, 12), (4, 13), (8, 8), (9, 12), (4, 7)):
+        lib.aws_reset_error()
+        assert lib.aws_huffman_amd_engine_new_fitted(C.byref(h), -1, lo, hi) == -1, (lo, hi)
+        assert lib.aws_last_error() == harness.AWS_ERROR_INVALID_ARGUMENT and h.value == 0x1234, (lo, hi)
+    # (the first device that does not exist: a node of eight has a device 7)
+    assert new_fitted(lib, 4, 12, device=lib.aws_huffman_amd_device_count())[:2] == INVALID
+    lib.aws_reset_error()
+    assert lib.aws_huffman_amd_engine_new_fitted(None, -1, 4, 12) == -1
+    assert lib.aws_last_error() == harness.AWS_ERROR_INVALID_ARGUMENT
+
+    eng = FittedEngine(lib, 5, 11)
+    patterns, lens = harness.load_table()
+    coder = lib.aws_huffman_amd_table_coder_new(patterns, lens)
+    plain = harness.Engine(lib, coder)
+    d_in, d_out, d_off = eng.alloc(4096), eng.alloc(4096), eng.alloc(64)
+    plan = dplan = None
+    try:
+        assert lib.aws_huffman_amd_engine_is_fitted(eng.h) and not lib.aws_huffman_amd_engine_is_fitted(plain.h)
+        assert lib.aws_huffman_amd_engine_max_code_bits(eng.h) == 11
+        assert lib.aws_huffman_amd_engine_can_decode(eng.h) and lib.aws_huffman_amd_engine_encodes_in_one_pass(eng.h)
+
+        def error_of(call, *args):
+            lib.aws_reset_error()
+            rc = call(*args)
+            return rc, lib.aws_last_error() if rc else 0
+
+        # NULL arguments, an engine with a coder
+        fit_counts, fit_lengths = lib.aws_huffman_amd_engine_fit_counts, lib.aws_huffman_amd_engine_fit_lengths
+        assert error_of(fit_counts, None, eng.d_counts, eng.d_bits, eng.d_status, None) == INVALID
+        assert error_of(fit_counts, eng.h, None, eng.d_bits, eng.d_status, None) == INVALID
+        assert error_of(fit_lengths, None, eng.d_bits, eng.d_status, None) == INVALID
+        assert error_of(fit_lengths, eng.h, None, eng.d_status, None) == INVALID
+        assert error_of(fit_counts, plain.h, eng.d_counts, eng.d_bits, eng.d_status, None) == INVALID
+        assert error_of(fit_lengths, plain.h, eng.d_bits, eng.d_status, None) == INVALID
+        assert error_of(lib.aws_huffman_amd_testing_engine_tables, eng.h, None, None, 1 << 11) == INVALID
+
+        # never fitted: plans are made (their geometry is the bounds'), no launch is taken, nothing is written
+        eng.fill(d_in, 0x41, 4096)
+        eng.fill(d_out, 0xC3, 4096)
+        eng.fill(d_off, 0xEE, 64)
+        plan = eng.encode_plan([dict(in_offset=0, in_len=1000, out_offset=0, out_capacity=2000)])
+        dplan = eng.decode_plan([dict(in_offset=0, in_len=1000, out_offset=0, out_capacity=2000)])
+        state = (-1, AWS_ERROR_INVALID_STATE)
+        assert error_of(lib.aws_huffman_amd_encode_plan_launch, plan, d_in, d_out, False, None) == state
+        assert error_of(lib.aws_huffman_amd_encode_plan_launch, plan, d_in, d_out, True, None) == state
+        assert error_of(lib.aws_huffman_amd_encode_plan_launch_packed, plan, d_in, d_out, 4096, d_off, 1, None) == state
+        assert error_of(lib.aws_huffman_amd_decode_plan_launch, dplan, d_in, d_out, None) == state
+        assert error_of(lib.aws_huffman_amd_decode_plan_launch_packed, dplan, d_in, d_out, 4096, d_off, 1, None) == state
+        eng.sync()
+        assert np.all(eng.download(d_out, 4096) == 0xC3) and np.all(eng.download(d_off, 64) == 0xEE)
+        # ... and behind the first fit the same plans are
+        status, _ = eng.fit_counts(printable_counts())
+        assert status == FIT_OK
+        assert error_of(lib.aws_huffman_amd_encode_plan_launch, plan, d_in, d_out, False, None) == (0, 0)
+        eng.sync()
+        # the status and the lengths are optional
+        assert error_of(fit_counts, eng.h, eng.d_counts, None, None, None) == (0, 0)
+        assert error_of(fit_lengths, eng.h, eng.d_bits, None, None) == (0, 0)
+        eng.sync()
+    finally:
+        if plan:
+            lib.aws_huffman_amd_encode_plan_destroy(plan)
+        if dplan:
+            lib.aws_huffman_amd_decode_plan_destroy(dplan)
+        for d in (d_in, d_out, d_off):
+            eng.free(d)
+        eng.close()
+        plain.close()
+        lib.aws_huffman_amd_table_coder_destroy(coder)
+
+
 # ----------------------------------------------------------------------------- data shapes, and a fitted engine against the oracle
 SHAPES = ["printable", "geometric", "uniform", "one byte"]
 PARITY_SIZES = [0, 1, 15, 300, 3000, 40000, 100003]  # nothing, a thread's or a wave's, three segments / two chunks, many
@@ -257,17 +384,58 @@ def decode_room(n_bytes, lengths):
     return n_bytes * 8 // min(lengths) + 8
 
 
-def run_parity(lib, oracle, eng, shape):
-    """test_fitted_engine_parity for one data shape on one fitted engine: the batch through every encode and decode launch,
-    record for record and byte for byte against the oracle's table coder of the canonical rows."""
+def parity_data(shape):
+    """The symbols run_parity fits and codes for `shape`: PARITY_SIZES items cut from one array."""
+    return shape_bytes(shape, sum(PARITY_SIZES), 41)
+
+
+def sweep_lengths(lib, bounds, shape):
+    """The host's lengths for parity_data(shape) under `bounds`: what run_parity's fit must come to (check_fit)."""
+    return host_lengths(lib, ba.bincount(parity_data(shape)), *bounds)
+
+
+def run_sweep_saw_a_spread(lib, cases):
+    """cases: the (bounds, shape) pairs a file's parity tests run.  Bounds with min_bits == 8 or max_bits == 8 give the flat
+    8-bit code whatever the data (Kraft, 256 coded symbols); every other pair of bounds must meet at least one shape whose
+    code has more than one length -- or the sweep tests flat codes only and says nothing of the bounds."""
+    seen = {}
+    for bounds, shape in cases:
+        seen.setdefault(bounds, {})[shape] = sorted(set(sweep_lengths(lib, bounds, shape)))
+    assert set(seen) == set(BOUNDS), sorted(set(BOUNDS) - set(seen))
+    for (lo, hi), by_shape in seen.items():
+        if only_flat(lo, hi):
+            assert all(ls == [8] for ls in by_shape.values()), ((lo, hi), by_shape)
+    flat_only = {b: by_shape for b, by_shape in seen.items() if not only_flat(*b) and all(len(ls) == 1 for ls in by_shape.values())}
+    assert not flat_only, "bounds whose shapes all fitted a flat code; the sets of lengths seen per pair: %r" % (seen,)
+
+
+def run_parity(lib, oracle, bounds, shape, road=None, decode=True):
+    """test_fitted_engine_parity for one data shape on one engine fitted within `bounds`, made under the encode road `road`
+    (harness.ENCODE_ROADS): the batch through every encode and (decode=True) decode launch, record for record and byte for
+    byte against the oracle's table coder of the canonical rows."""
+    with harness.encode_road(lib, road):
+        eng = FittedEngine(lib, *bounds)
+    try:
+        _parity(lib, oracle, eng, shape, road, decode)
+    finally:
+        eng.close()
+
+
+def _parity(lib, oracle, eng, shape, road, decode):
+    want_road = ROAD_OF[road]
     rng = np.random.default_rng(SHAPES.index(shape) + 500)
-    data = shape_bytes(shape, sum(PARITY_SIZES), 41)
+    data = parity_data(shape)
     cuts = np.cumsum([0] + PARITY_SIZES)
     blobs = [data[a:b].copy() for a, b in zip(cuts[:-1], cuts[1:])]
     n = len(blobs)
-    fit = Fit(lib, oracle, eng, ba.bincount(data), shape)
-    assert is_flat(fit.lengths) == (shape == "uniform"), sorted(set(fit.lengths))
-    assert lib.aws_huffman_amd_engine_encodes_in_one_pass(eng.h)
+    fit = Fit(lib, oracle, eng, ba.bincount(data), shape)  # (the device's lengths are the host's: check_fit)
+    if only_flat(eng.lo, eng.hi):
+        assert fit.lengths == [8] * 256, (eng.lo, eng.hi, sorted(set(fit.lengths)))
+    if (eng.lo, eng.hi) == (4, 12):
+        assert is_flat(fit.lengths) == (shape == "uniform"), sorted(set(fit.lengths))
+    assert min(fit.lengths) >= eng.lo and max(fit.lengths) <= eng.hi
+    # (the one-pass rule reads the bounds, 4 <= min_bits and max_bits <= 12 for every fitted engine; the road switch decides)
+    assert bool(lib.aws_huffman_amd_engine_encodes_in_one_pass(eng.h)) == (road != "three-kernel")
     host_in, in_offs = pa.lay_out(blobs, rng, first=1)
     enc_lens = pa.encoded_lengths(fit.code_lens, blobs, [0] * n)
     caps = [int(l) + 2 for l in enc_lens]
@@ -282,15 +450,19 @@ def run_parity(lib, oracle, eng, shape):
     plans, extra = [], []
     try:
         stats = eng.encode_stats(plan)
-        assert stats["by_thread"] >= 2 and stats["by_wave"] >= 1 and stats["by_pieces"] >= 2, stats
+        if road != "three-kernel":
+            assert stats["by_thread"] >= 2 and stats["by_wave"] >= 1 and stats["by_pieces"] >= 2, stats
+        else:  # (no bound decides this one but the road: count / scan / pack has no wave's class, the 3000 symbols go by pieces)
+            assert stats["by_thread"] >= 2 and stats["by_wave"] == 0 and stats["by_pieces"] >= 3, stats
+        label = "%s %r %s" % (shape, (eng.lo, eng.hi), road)
         # the packed launch, then the plain one (whose output the decodes below read)
-        pa.check_launch(oracle, fit.ocoder, eng, plan, d_in, blobs, fit.code_lens, overflows, eoss, 1, want_road=ROAD_ONE_PASS,
-                        label=shape)
+        pa.check_launch(oracle, fit.ocoder, eng, plan, d_in, blobs, fit.code_lens, overflows, eoss, 1, want_road=want_road,
+                        label=label)
         eng.fill(d_out, pa.MARKER, out_size)
         eng.encode_launch(plan, d_in, d_out)
         got = eng.download(d_out, out_size)
         res = eng.encode_results(plan, n)
-        assert eng.encode_road(plan) == ROAD_ONE_PASS
+        assert eng.encode_road(plan) == want_road, (label, eng.encode_road(plan))
         want = np.full(out_size, pa.MARKER, np.uint8)
         streams = []
         for i in range(n):
@@ -298,7 +470,9 @@ def run_parity(lib, oracle, eng, shape):
             assert res[i] == rec and rec[:2] == (0, 0) and rec[3] == enc_lens[i], (shape, i, res[i], rec)
             want[out_offs[i]:out_offs[i] + caps[i]] = enc
             streams.append((enc[:rec[3]].copy(), 0))
-        assert np.array_equal(got, want), (shape, int(np.flatnonzero(got != want)[0]))
+        assert np.array_equal(got, want), (label, int(np.flatnonzero(got != want)[0]))
+        if not decode:
+            return
 
         def check_back(dplan, label):
             eng.fill(d_back, pa.MARKER, host_in.size)
@@ -312,9 +486,9 @@ def run_parity(lib, oracle, eng, shape):
                 assert np.array_equal(syms, blobs[i])
                 want_back[in_offs[i]:in_offs[i] + blobs[i].size] = syms
             assert np.array_equal(back, want_back), (shape, label, int(np.flatnonzero(back != want_back)[0]))
+            # (chunked whatever the code is: the road is the bounds', a flat code in a fitted engine has no road of its own)
             dstats = eng.decode_stats(dplan)
-            if not is_flat(fit.lengths):
-                assert dstats["by_pieces"] > 0, (shape, label, dstats)
+            assert dstats["by_pieces"] > 0 and dstats["by_blocks"] == 0, (shape, label, dstats)
 
         # decode: a plan of host items, a plan chained to the encode plan, a packed launch over offsets and lengths
         dplan = eng.decode_plan([dict(in_offset=out_offs[i], in_len=int(enc_lens[i]), out_offset=in_offs[i],
@@ -389,11 +563,16 @@ def run_refit_between_launches(lib, oracle, eng, n_bytes):
                              for i in range(n)])
     try:
         st = eng.stream
+        # (plans depend on the bounds alone: what they report is the same behind either fit)
+        estats, dstats = [eng.encode_stats(plan)], [eng.decode_stats(dplan)]
         for k in range(2):
             assert eng.fit_counts_async(d_counts[k], st) == (0, 0)
             assert lib.aws_huffman_amd_encode_plan_launch(plan, d_in, d_out[k], False, st) == 0
+            estats.append(eng.encode_stats(plan))
         eng.sync()
         res = eng.encode_results(plan, n)
+        estats.append(eng.encode_stats(plan))
+        assert all(e == estats[0] for e in estats), estats
         bufs = [eng.download(d_out[k], out_size) for k in range(2)]
         for k in range(2):
             for i in range(n):
@@ -406,8 +585,11 @@ def run_refit_between_launches(lib, oracle, eng, n_bytes):
         for k in range(2):
             assert eng.fit_counts_async(d_counts[k], st) == (0, 0)
             assert lib.aws_huffman_amd_decode_plan_launch(dplan, d_out[k], d_back[k], st) == 0
+            dstats.append(eng.decode_stats(dplan))
         eng.sync()
         dres = eng.decode_results(dplan, n)
+        dstats.append(eng.decode_stats(dplan))
+        assert all(d == dstats[0] for d in dstats), dstats
         for k in range(2):
             back = eng.download(d_back[k], n_bytes)
             assert np.array_equal(back, data), ("decode", k, int(np.flatnonzero(back != data)[0]))
@@ -419,6 +601,84 @@ def run_refit_between_launches(lib, oracle, eng, n_bytes):
         lib.aws_huffman_amd_decode_plan_destroy(dplan)
         for d in [d_in] + d_counts + d_out + d_back:
             eng.free(d)
+
+
+# ----------------------------------------------------------------------------- a receiver's code, whatever lengths it was sent
+RECEIVER_CODES = [  # (bounds, 256 lengths): Kraft sum at most 1 by arithmetic, most of them below 1 (windows without a code)
+    ((8, 12), [9] * 256), ((4, 10), [8] * 255 + [9]), ((4, 12), [9] * 256), ((8, 12), [8] * 255 + [12]),
+    ((4, 12), [5] * 16 + [9] * 240), ((4, 8), [8] * 256),
+    ((4, 11), [11] * 256), ((7, 9), [7] * 64 + [9] * 192), ((6, 11), [6] * 32 + [11] * 224)]
+
+
+def receiver_id(case):
+    (lo, hi), lengths = case
+    runs = []
+    for l in lengths:
+        if runs and runs[-1][0] == l:
+            runs[-1][1] += 1
+        else:
+            runs.append([l, 1])
+    return "%d..%d:" % (lo, hi) + "+".join("%dx%d" % (c, l) for l, c in runs)
+
+
+def run_receiver_codes(lib, oracle, bounds, lengths, kinds=("matched", "uniform"), enc_bytes=120_000):
+    """An engine within `bounds` fitted by aws_huffman_amd_engine_fit_lengths from `lengths` (any the interface takes: the
+    Kraft sum may be below 1, the decode table then has windows without a code).  Symbols drawn by 2^-length ("matched") and evenly
+    ("uniform"), about enc_bytes encoded (three to four decode chunks): one plan encode against the oracle's table coder of the
+    canonical rows; the stream whole, damaged, overwritten with ones and with zeros, cut, short of room, its first bytes,
+    entered inside a byte, and arbitrary bytes through three decode roads, every record and byte the oracle's; both
+    tables against the rows."""
+    lo, hi = bounds
+    assert len(lengths) == 256 and all(lo <= l <= hi for l in lengths), bounds
+    assert sum(1 << (hi - l) for l in lengths) <= 1 << hi, "Kraft sum above 1"
+    shortest = min(lengths)
+    rows = host_rows(lib, lengths)
+    ocoder = oracle_coder(oracle, rows)
+    w = types.SimpleNamespace(oracle=oracle)  # (all that parity_cases.decode_items_like_the_oracle asks of a World)
+    eng = FittedEngine(lib, lo, hi)
+    try:
+        assert eng.fit_lengths(lengths) == FIT_OK
+        for kind in kinds:
+            rng = np.random.default_rng([601, lo, hi, ("matched", "uniform").index(kind)])
+            data = pc.shape_data(rng, lengths, kind, enc_bytes)
+            n = int(data.size)
+            enc = oracle.encode_all(ocoder, data, eos_padding=0xFF)
+            # ---- encode: a plan of one item
+            cap = int(enc.size) + 8
+            d_in, d_out = eng.alloc(n), eng.alloc(cap + 8)
+            plan = eng.encode_plan([dict(in_offset=0, in_len=n, out_offset=3, out_capacity=cap, eos_padding=0xFF)])
+            try:
+                eng.upload(d_in, data)
+                eng.fill(d_out, pa.MARKER, cap + 8)
+                eng.encode_launch(plan, d_in, d_out)
+                rec, want = pa.oracle_item(oracle, ocoder, data, (0, 0), 0xFF, cap)
+                assert rec[:4] == (0, 0, n, enc.size) and np.array_equal(want[:enc.size], enc)
+                assert eng.encode_results(plan, 1) == [rec], (bounds, kind)
+                out = eng.download(d_out, cap + 8)
+                assert np.array_equal(out[3:3 + cap], want) and np.all(out[:3] == pa.MARKER) and np.all(out[3 + cap:] == pa.MARKER)
+            finally:
+                lib.aws_huffman_amd_encode_plan_destroy(plan)
+                eng.free(d_in)
+                eng.free(d_out)
+            # ---- decode
+            third, half = enc.size // 3, enc.size // 2
+            damaged, ones, zeros = enc.copy(), enc.copy(), enc.copy()
+            damaged[half:half + 4] ^= 0xA5
+            ones[third:third + 6] = 0xFF
+            zeros[third:third + 6] = 0x00
+            inside = enc[5:5 + 70000]
+            noise = rng.integers(0, 256, 40000).astype(np.uint8)
+            streams = [(enc, 0, n), (damaged, 0, n), (ones, 0, n), (zeros, 0, n), (enc[:third + 5], 0, n), (enc, 0, n // 2 + 3),
+                       (enc[:700], 0, 700 * 8 // shortest + 8), (inside, 3, inside.size * 8 // shortest + 8),
+                       (noise, 0, noise.size * 8 // shortest + 8)]
+            pc.decode_items_like_the_oracle(w, eng, ocoder, streams, rng, "receiver %r, %s data" % (bounds, kind),
+                                            modes=(None, "long-way", "tails-apart"), kinds=2)
+        enc_table, lut = eng.tables()
+        want_enc, want_lut = expected_tables(rows, hi)
+        assert np.array_equal(enc_table, want_enc) and np.array_equal(lut, want_lut), bounds
+    finally:
+        eng.close()
+        oracle.lib.oracle_table_coder_destroy(ocoder)
 
 
 # ----------------------------------------------------------------------------- chains on one stream (the GPU tests)

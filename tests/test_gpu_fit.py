@@ -1,6 +1,9 @@
 """The coder fitted on the device (huffman_amd_fit.h, fit_kernels.hip) on an MI355X (`pytest -m gpu`): lengths and tables
 against the host's, count -> fit -> packed encode chained on one stream and captured in a graph against the oracle, a
-receiver fitted from the 256 lengths, and a refit between two launches of one plan with no host wait."""
+receiver fitted from the 256 lengths, and a refit between two launches of one plan with no host wait.  Then the scenarios
+of tests/fit_api.py that tests/test_emulated_fit.py runs on the emulator, here at the same sizes: a fitted engine against
+the oracle within every pair of bounds, under the encode roads, receivers of codes with windows without a code, the
+refusals of a fit and the never-fitted state."""
 import ctypes as C
 
 import numpy as np
@@ -139,3 +142,49 @@ def test_refit_between_launches_of_one_plan(lib, oracle):
         fa.run_refit_between_launches(lib, oracle, eng, 4 * MiB)
     finally:
         eng.close()
+
+
+# ----------------------------------------------------------------------------- the emulator's scenarios, on the chip
+SWEEP = [(b, s) for b in fa.BOUNDS for s in fa.SHAPES]
+
+
+@pytest.mark.parametrize("bounds,shape", SWEEP, ids=["%d..%d-%s" % (b + (s,)) for b, s in SWEEP])
+def test_fitted_engine_parity(lib, oracle, bounds, shape):
+    fa.run_parity(lib, oracle, bounds, shape)
+
+
+def test_the_sweep_saw_a_spread_of_lengths(lib):
+    fa.run_sweep_saw_a_spread(lib, SWEEP)
+
+
+@pytest.mark.parametrize("shape", ["printable", "one byte"])
+@pytest.mark.parametrize("road", ["three-kernel", "one-pass-fails"])
+def test_fitted_engine_made_under_an_encode_road(lib, oracle, road, shape):
+    fa.run_parity(lib, oracle, (4, 12), shape, road=road, decode=False)
+
+
+@pytest.mark.parametrize("kind", ["matched", "uniform"])
+@pytest.mark.parametrize("case", fa.RECEIVER_CODES, ids=fa.receiver_id)
+def test_receiver_codes(lib, oracle, case, kind):
+    fa.run_receiver_codes(lib, oracle, *case, kinds=(kind,))
+
+
+def test_fit_lengths(lib):
+    first = fa.FittedEngine(lib, 4, 12)
+    try:
+        fa.run_fit_lengths(lib, first)
+    finally:
+        first.close()
+
+
+def test_refit_between_launches_of_one_small_plan(lib, oracle):
+    """(the emulator's size: items of a wave's and a chunk's length beside the long one)"""
+    eng = fa.FittedEngine(lib, 4, 12)
+    try:
+        fa.run_refit_between_launches(lib, oracle, eng, 120_001)
+    finally:
+        eng.close()
+
+
+def test_interface_errors(lib):
+    fa.run_interface_errors(lib)

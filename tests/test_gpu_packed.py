@@ -1,7 +1,8 @@
 """Packed batch encode on an MI355X (`pytest -m gpu`): the BASELINE batch of 65 536 x 16 KiB, a million header-sized
 items and one 1 GiB item at full size -- offsets against a numpy table sum of the code lengths, a sample of items byte
 for byte against the oracle, everything round-tripped through the chained decode --, odd lengths at align 1 on both
-encode roads, and a packed launch captured in a graph and replayed on new input."""
+encode roads, and a packed launch captured in a graph and replayed on new input.  Then the edge scenarios of
+tests/packed_api.py that tests/test_emulated_packed.py runs on the emulator, here at the same sizes."""
 import hashlib
 
 import numpy as np
@@ -212,3 +213,45 @@ def test_captured_graph(world, eng):
         eng.lib.aws_huffman_amd_encode_plan_destroy(plan)
         for p in (d_in, d_out, d_off):
             eng.free(p)
+
+
+# ----------------------------------------------------------------------------- the emulator's scenarios, on the chip
+@pytest.fixture(scope="module")
+def scene(oracle, lib):
+    s = pa.Scene(oracle, lib)
+    yield s
+    s.close()
+
+
+def test_offsets_and_bytes(scene):
+    pa.offsets_and_bytes(scene)
+
+
+@pytest.mark.parametrize("road,want_road", pa.ENCODE_ROADS)
+@pytest.mark.parametrize("kind", pa.ENCODE_PLAN_KINDS)
+def test_every_plan_and_road(scene, kind, road, want_road):
+    pa.every_plan_and_road(scene, kind, road, want_road)
+
+
+@pytest.mark.parametrize("tile,count", [(tile, n) for tile, counts in pa.SCAN_TILES for n in counts])
+def test_scan_boundaries(scene, tile, count):
+    pa.scan_boundaries(scene, tile, (count,))
+
+
+@pytest.mark.parametrize("align", [1, 16])
+@pytest.mark.parametrize("road", [None, "three-kernel"])
+def test_capacity_clipping(scene, road, align):
+    pa.capacity_clipping(scene, road, aligns=(align,))
+
+
+def test_coder_with_holes(scene):
+    pa.coder_with_holes(scene)
+
+
+def test_the_plans_own_layout_survives(scene):
+    pa.the_plans_own_layout_survives(scene)
+
+
+@pytest.mark.parametrize("shape", ["threads", "chunks"])
+def test_round_trip_through_a_chained_decode(scene, shape):
+    pa.round_trip_through_a_chained_decode(scene, shape)

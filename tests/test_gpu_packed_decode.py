@@ -2,13 +2,16 @@
 BASELINE batch of 65 536 x 16 KiB, a million header-sized items and one 1 GiB item at full size -- the plan made from the
 packed buffer's offsets on the device, the output laid out by the device, symbol counts of a sample against the oracle,
 every item's symbols against the original --, odd lengths at align 1 with every output byte against the oracle, and a
-packed launch captured in a graph and replayed on new input."""
+packed launch captured in a graph and replayed on new input.  Then the edge scenarios of tests/packed_decode_api.py that
+tests/test_emulated_packed_decode.py runs on the emulator, here at the same sizes: other coders, streams that stop early,
+clipped capacities, the decode roads and every way a plan is made under a packed launch."""
 import ctypes as C
 import hashlib
 
 import numpy as np
 import pytest
 
+import build_api as ba
 import harness
 import packed_api as pa
 import packed_decode_api as pd
@@ -288,3 +291,49 @@ def test_captured_graph(world, eng):
         eng.lib.aws_huffman_amd_decode_plan_destroy(plan)
         for p in (d_in, d_out, d_off, d_offs, d_lens):
             eng.free(p)
+
+
+# ----------------------------------------------------------------------------- the emulator's scenarios, on the chip
+@pytest.fixture(scope="module")
+def scene(oracle, lib):
+    s = pa.Scene(oracle, ba.bind(lib))
+    yield s
+    s.close()
+
+
+def test_mixed_batch(scene):
+    pd.mixed_batch(scene)
+
+
+def test_streams_that_stop_early(scene):
+    pd.streams_that_stop_early(scene)
+
+
+@pytest.mark.parametrize("align", [1, 16])
+@pytest.mark.parametrize("road", [None, "long-way"])
+def test_capacity_clipping(scene, road, align):
+    pd.capacity_clipping(scene, road, aligns=(align,))
+
+
+@pytest.mark.parametrize("name", pd.OTHER_CODERS)
+def test_other_coders(scene, name):
+    pd.other_coders(scene, name)
+
+
+@pytest.mark.parametrize("kind", pd.DECODE_PLAN_KINDS)
+def test_every_way_a_plan_is_made(scene, kind):
+    pd.every_way_a_plan_is_made(scene, kind)
+
+
+@pytest.mark.parametrize("road", pd.DECODE_ROADS)
+def test_decode_road_switches(scene, road):
+    pd.decode_road_switches(scene, road)
+
+
+@pytest.mark.parametrize("tile,count", [(tile, n) for tile, counts in pa.SCAN_TILES for n in counts])
+def test_scan_boundaries(scene, tile, count):
+    pd.scan_boundaries(scene, tile, (count,))
+
+
+def test_the_plans_own_layout_survives(scene):
+    pd.the_plans_own_layout_survives(scene)
