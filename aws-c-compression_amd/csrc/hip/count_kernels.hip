@@ -12,8 +12,12 @@
  * l mod 32.  A ds_add_u32 of a wave is served in two groups of 32 lanes, and a group's 32 addresses then lie in 32
  * different banks ((a / 4) mod 32) whatever the bytes are: uniform bytes and one repeated byte cost the same LDS cycles
  * (with one copy a wave, 32 lanes on one bin take turns; profiles/tools/micro/probe_counts.hip measures both layouts).
+ *
+ * The same kernel has a second body, chosen by a launch argument: the hot pass of the block index (index_block_bits.hpp,
+ * hufk_block_bits below), which reads the same bytes the same way and looks code lengths up where this one counts.
  */
 #include "kernels_common.hpp"
+#include "index_block_bits.hpp"
 #include "launch_common.hpp"
 
 namespace {
@@ -54,7 +58,11 @@ __device__ __forceinline__ void count_flush(u32 *tab, u64 *counts) {
  * steps_per_flush: steps of kCountStepBytes a workgroup reads between two flushes (>= 1) */
 __global__ __launch_bounds__(kCountThreads) void count_kernel(
     const u8 *head, u32 head_len, const uint4 *body, u64 n_vec, const u8 *tail, u32 tail_len, u64 *counts,
-    u64 steps_per_flush) {
+    u64 steps_per_flush, index_job index) {
+    if (index.index) { /* (the same in every thread of the launch) */
+        index_block_bits(index);
+        return;
+    }
     u32 *tab = reinterpret_cast<u32 *>(dyn_lds);
     const u32 t = threadIdx.x;
     if (t < 256) {
@@ -129,7 +137,34 @@ int hufk_symbol_counts(const void *input, uint64_t length, uint64_t *counts, uin
     per_flush = per_flush ? per_flush : 1;
     hipLaunchKernelGGL(
         count_kernel, dim3(grid), dim3(kCountThreads), kCountLdsBytes, (hipStream_t)stream, in, (u32)head_len,
-        reinterpret_cast<const uint4 *>(in + head_len), n_vec, in + head_len + n_vec * 16u, (u32)tail_len, counts, per_flush);
+        reinterpret_cast<const uint4 *>(in + head_len), n_vec, in + head_len + n_vec * 16u, (u32)tail_len, counts, per_flush,
+        index_job{});
+    return (int)hipGetLastError();
+}
+
+int hufk_block_bits(
+    const uint64_t *enc_table, const void *input, uint64_t length, uint64_t block_symbols, uint64_t *index, void *stream) {
+    static_assert(kIndexThreads == kCountThreads, "one kernel, one workgroup size");
+    const u64 n_blocks = (length + block_symbols - 1) / block_symbols;
+    if (n_blocks == 0) {
+        return 0;
+    }
+    index_job job{};
+    job.enc_table = enc_table;
+    job.in = (const u8 *)input;
+    job.length = length;
+    job.block_symbols = block_symbols;
+    job.groups_per_block = (u32)(block_symbols / 16);
+    job.tile_blocks = (u32)(block_symbols < kIndexStepBytes ? kIndexStepBytes / block_symbols : 1u);
+    job.inverse = job.tile_blocks > 1 ? (u32)(((1ull << 32) + job.groups_per_block - 1) / job.groups_per_block) : 0u;
+    job.n_tiles = (n_blocks + job.tile_blocks - 1) / job.tile_blocks;
+    job.n_blocks = n_blocks;
+    job.index = index;
+    const uint32_t grid = hufk_host::persistent_grid(
+        count_kernel, kCountThreads, kIndexLdsBytes, (uint32_t)(job.n_tiles < 0xFFFFFFFFull ? job.n_tiles : 0xFFFFFFFFull));
+    hipLaunchKernelGGL(
+        count_kernel, dim3(grid), dim3(kCountThreads), kIndexLdsBytes, (hipStream_t)stream, (const u8 *)nullptr, 0u,
+        (const uint4 *)nullptr, (u64)0, (const u8 *)nullptr, 0u, (u64 *)nullptr, (u64)1, job);
     return (int)hipGetLastError();
 }
 

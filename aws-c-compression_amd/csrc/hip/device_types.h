@@ -221,11 +221,18 @@ struct hufd_chunk_rec {
 };
 
 /* Where the items of a plan that is made on the device come from (plan_kernels.hip): the caller's records in DEVICE memory,
- * a stride, what an encode launch left, or a packed buffer's offsets (decode) */
+ * a stride, what an encode launch left, a packed buffer's offsets or ranges of an indexed stream's blocks (decode) */
 #define HUFD_ITEMS_DEVICE_ARRAY 0u
 #define HUFD_ITEMS_STRIDED 1u
 #define HUFD_ITEMS_FROM_ENCODE 2u
 #define HUFD_ITEMS_PACKED_INPUT 3u
+#define HUFD_ITEMS_BLOCK_RANGES 4u
+/* a range of whole blocks of an indexed stream, as the public header lays it out (struct aws_huffman_amd_block_range) */
+struct hufd_block_range {
+    uint64_t first_block;
+    uint64_t block_count;
+    uint64_t out_offset;
+};
 struct hufd_item_source {
     uint32_t kind;
     uint32_t first_bit;   /* strided, decode */
@@ -241,6 +248,12 @@ struct hufd_item_source {
      * packed_offsets[i + 1] -- from bit 0, and has no room of its own (such a plan is for packed launches) */
     const uint64_t *packed_offsets;
     const uint64_t *packed_lengths;
+    /* ranges of whole blocks of ONE indexed stream (decode, huffman_amd_index.h): item i is block_ranges[i] of the stream of
+     * stream_symbols symbols whose block k starts at bit block_index[k] (n_blocks + 1 entries) of the encoded_length bytes
+     * that lie encoded_offset bytes behind the input base */
+    const uint64_t *block_index;
+    const struct hufd_block_range *block_ranges;
+    uint64_t n_blocks, stream_symbols, block_symbols, encoded_offset, encoded_length;
 };
 
 #endif /* HUFFMAN_AMD_DEVICE_TYPES_H */

@@ -252,6 +252,24 @@ int hufk_fit_tables(
     uint32_t from_lengths, const uint64_t *counts, const uint8_t *lengths, uint32_t min_bits, uint32_t max_bits, uint64_t *enc_table,
     uint16_t *dec_lut, uint8_t *num_bits_out, uint32_t *status, void *stream);
 
+/* The block index of a stream (index_kernels.hip, huffman_amd_index.h): index[k] = the code bits of symbols
+ * [0, min(k * block_symbols, length)) under enc_table, k = 0 .. n_blocks = ceil(length / block_symbols), 1 <= n_blocks < 2^32;
+ * *status (NULL: not wanted) says whether a symbol without a code was met (it counts 0 bits).  block_symbols: a multiple of
+ * 64 up to 1 << 24.  tile_sums: scratch of 2 * HUFK_INDEX_MAX_TILES words; tile_blocks: the entries a workgroup of the scan
+ * takes, from hufk_index_tile_blocks (asked: the tests' own number, 0: the rule; never more than HUFK_INDEX_MAX_TILES tiles).
+ * Its two steps: _block_bits (count_kernels.hip) leaves index[k] = the bits of block k alone, bit 63 set on some entry where
+ * a symbol without a code was met; _index_scan (pack_kernels.hip) sums them in place and writes index[n_blocks] and *status. */
+#define HUFK_INDEX_OK 0u
+#define HUFK_INDEX_SYMBOL_WITHOUT_CODE 1u
+#define HUFK_INDEX_MAX_TILES 8192u
+uint32_t hufk_index_tile_blocks(uint32_t n_blocks, uint32_t asked);
+int hufk_block_index(
+    const uint64_t *enc_table, const void *input, uint64_t length, uint64_t block_symbols, uint32_t tile_blocks, uint64_t *index,
+    uint64_t *tile_sums, uint32_t *status, void *stream);
+int hufk_block_bits(
+    const uint64_t *enc_table, const void *input, uint64_t length, uint64_t block_symbols, uint64_t *index, void *stream);
+int hufk_index_scan(uint64_t *index, uint32_t n_blocks, uint32_t tile_blocks, uint64_t *tile_sums, uint32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -85,9 +85,24 @@ struct pack_decode {
     }
 };
 
+/* A third kind of batch (`decode` == kPackIndex), the block index of a stream (index_kernels.hip, huffman_amd_index.h): "item"
+ * i is block i, its length the code bits index_block_bits left in index[i], scanned in place -- a thread reads index[i] in
+ * front of the scan's barriers and writes the same word behind them; nothing to place.  Bit 63 of an entry says that a
+ * symbol without a code was met: it travels where the other kinds' largest length travels, and ends in a status word */
+constexpr u32 kPackIndex = 2;
+constexpr u64 kPackIndexHole = 1ull << 63;
+
 __device__ __forceinline__ u64 pack_length(const void *lengths, u32 decode, u64 i) {
+    if (decode == kPackIndex) {
+        return reinterpret_cast<const u64 *>(lengths)[i] & ~kPackIndexHole;
+    }
     return decode ? pack_decode::length(reinterpret_cast<const pack_decode::measured *>(lengths), i)
                   : pack_encode::length(reinterpret_cast<const pack_encode::measured *>(lengths), i);
+}
+
+/* what an item adds to the maximum: its reserved length, or the index entry as it stands (bit 63 and all) */
+__device__ __forceinline__ u64 pack_most(const void *lengths, u32 decode, u64 i, u64 reserved) {
+    return decode == kPackIndex ? reinterpret_cast<const u64 *>(lengths)[i] : reserved;
 }
 
 __device__ __forceinline__ u64 pack_reserved(const void *lengths, u32 decode, u64 i, u64 align_mask) {
@@ -155,8 +170,9 @@ __global__ __launch_bounds__(kPackThreads) void pack_tile_sums_kernel(
     u64 sum = 0, most = 0;
     for (u64 i = lo + threadIdx.x; i < hi; i += kPackThreads) {
         const u64 r = pack_reserved(lengths, decode, i, align_mask);
+        const u64 m = pack_most(lengths, decode, i, r);
         sum += r;
-        most = r > most ? r : most;
+        most = m > most ? m : most;
     }
     pack_block_sum_max(sum, most, slots);
     if (threadIdx.x == 0) {
@@ -184,20 +200,21 @@ __global__ __launch_bounds__(kPackThreads) void pack_offsets_kernel(
     for (u64 round = lo; round < hi; round += kPackThreads) { /* (the same trips in every thread: the scan has barriers) */
         const u64 i = round + threadIdx.x;
         const u64 reserved = i < hi ? pack_reserved(lengths, decode, i, align_mask) : 0;
+        const u64 marked = i < hi ? pack_most(lengths, decode, i, reserved) : 0;
         u64 total = 0;
         const u64 off = at + pack_block_exclusive_sum(reserved, slots, total);
         if (i < hi) {
-            if (decode) {
+            if (decode == 1) {
                 pack_decode::place(
                     reinterpret_cast<const pack_decode::item *>(items) + i, reinterpret_cast<pack_decode::item *>(packed) + i, off,
                     pack_length(lengths, decode, i), reserved, capacity);
-            } else {
+            } else if (decode == 0) {
                 pack_encode::place(
                     reinterpret_cast<const pack_encode::item *>(items) + i, reinterpret_cast<pack_encode::item *>(packed) + i, off, 0,
                     reserved, capacity);
             }
             offsets[i] = off; /* (never clipped: what the caller would have needed) */
-            mine = reserved > mine ? reserved : mine;
+            mine = marked > mine ? marked : mine;
         }
         at += total;
     }
@@ -206,8 +223,15 @@ __global__ __launch_bounds__(kPackThreads) void pack_offsets_kernel(
         pack_block_sum_max(unused, mine, slots + kPackWaves);
         if (threadIdx.x == 0) {
             offsets[n_items] = at;
-            summary[0] = at;
-            summary[1] = mine > most ? mine : most;
+            if (decode == kPackIndex) {
+                if (summary) { /* (the caller's status word: four bytes) */
+                    *reinterpret_cast<u32 *>(summary) =
+                        ((mine | most) & kPackIndexHole) ? HUFK_INDEX_SYMBOL_WITHOUT_CODE : HUFK_INDEX_OK;
+                }
+            } else {
+                summary[0] = at;
+                summary[1] = mine > most ? mine : most;
+            }
         }
     }
 }
@@ -280,6 +304,12 @@ int hufk_pack_offsets(
     uint64_t capacity, uint64_t *tile_sums, uint64_t *offsets, struct hufd_enc_item *packed, uint64_t *summary, void *stream) {
     return pack_offsets_launch(
         items, lengths, 0u, n_items, tile_items, align, capacity, tile_sums, offsets, packed, summary, (hipStream_t)stream);
+}
+
+int hufk_index_scan(uint64_t *index, uint32_t n_blocks, uint32_t tile_blocks, uint64_t *tile_sums, uint32_t *status, void *stream) {
+    return pack_offsets_launch(
+        nullptr, index, kPackIndex, n_blocks, tile_blocks, 1, 0, tile_sums, index, nullptr, reinterpret_cast<uint64_t *>(status),
+        (hipStream_t)stream);
 }
 
 int hufk_unpack_blank(const struct hufd_dec_item *items, uint32_t n_items, struct hufd_dec_item *packed, void *stream) {

@@ -83,6 +83,31 @@ __device__ __forceinline__ raw_item load_item(const hufd_item_source &src, u32 i
         r.out_off = 0;
         r.out_cap = 0;
         r.bits = 0;
+    } else if (!ENC && src.kind == HUFD_ITEMS_BLOCK_RANGES) {
+        /* item i = blocks [b0, b1) of an indexed stream: from the byte that holds bit index[b0] to the one that holds bit
+         * index[b1] - 1, entered inside its first byte, with room for the blocks' symbols and no more.  A range past the
+         * last block, an index that decreases from its first entry to its last or ends behind the stream's bytes: no item */
+        const hufd_block_range g = src.block_ranges[i];
+        r.in_off = 0;
+        r.in_len = 0;
+        r.out_off = g.out_offset;
+        r.out_cap = 0;
+        r.bits = 0;
+        r.bad = 1;
+        if (g.first_block <= src.n_blocks && g.block_count <= src.n_blocks - g.first_block) {
+            const u64 from = src.block_index[g.first_block], to = src.block_index[g.first_block + g.block_count];
+            const u64 first_byte = from / 8, end_byte = to / 8 + (to % 8 ? 1 : 0);
+            if (to >= from && end_byte <= src.encoded_length) {
+                r.bad = 0;
+                if (g.block_count) { /* (none: an empty item) */
+                    const u64 lo = g.first_block * src.block_symbols, hi = (g.first_block + g.block_count) * src.block_symbols;
+                    r.in_off = src.encoded_offset + first_byte;
+                    r.in_len = end_byte - first_byte; /* (4 GiB or more: refused with every such item) */
+                    r.bits = (u32)(from % 8);
+                    r.out_cap = (hi < src.stream_symbols ? hi : src.stream_symbols) - lo;
+                }
+            }
+        }
     } else if (ENC) {
         const hufd_raw_enc_item e = reinterpret_cast<const hufd_raw_enc_item *>(src.raw)[i];
         r.in_off = e.in_offset;

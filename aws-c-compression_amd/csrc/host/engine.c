@@ -9,6 +9,7 @@
 
 #include <aws/compression/huffman_amd_build.h>
 #include <aws/compression/huffman_amd_fit.h>
+#include <aws/compression/huffman_amd_index.h>
 #include <aws/compression/huffman_amd_packed.h>
 
 #include <assert.h>
@@ -507,6 +508,7 @@ void aws_huffman_amd_engine_destroy(struct aws_huffman_amd_engine *eng) {
     hufs_free(eng->d_enc_table);
     hufs_free(eng->d_dec_lut);
     hufs_free(eng->d_deep_lut);
+    hufs_free(eng->d_index_tile_sums);
     hufs_event_destroy(eng->fork_event);
     hufs_event_destroy(eng->join_event);
     if (eng->side_stream) {
@@ -2040,6 +2042,38 @@ static int dec_items_to_host(
         }
         free(at);
         free(len);
+    } else if (src->kind == HUFD_ITEMS_BLOCK_RANGES) {
+        /* (the index whole: 8 bytes a block; load_item of plan_kernels.hip is the rule this loop restates) */
+        struct hufd_block_range *ranges = malloc((n_items ? n_items : 1) * sizeof(*ranges));
+        uint64_t *index = malloc(((size_t)src->n_blocks + 1) * sizeof(*index));
+        e = ranges && index ? 0 : 2;
+        if (!e && n_items) {
+            e = hufs_copy_d2h(ranges, src->block_ranges, n_items * sizeof(*ranges), st);
+        }
+        if (!e && n_items) {
+            e = hufs_copy_d2h(index, src->block_index, ((size_t)src->n_blocks + 1) * sizeof(*index), st);
+        }
+        if (!e) {
+            e = hufs_stream_sync(st);
+        }
+        for (size_t i = 0; i < n_items && !e; ++i) {
+            const uint64_t b0 = ranges[i].first_block, count = ranges[i].block_count;
+            items[i].out_offset = ranges[i].out_offset;
+            items[i].in_len = UINT64_MAX; /* (a length no plan takes) */
+            if (b0 <= src->n_blocks && count <= src->n_blocks - b0) {
+                const uint64_t from = index[b0], to = index[b0 + count];
+                const uint64_t first_byte = from / 8, end_byte = to / 8 + (to % 8 ? 1 : 0);
+                if (to >= from && end_byte <= src->encoded_length) {
+                    const uint64_t lo = b0 * src->block_symbols, hi = (b0 + count) * src->block_symbols;
+                    items[i].in_len = count ? end_byte - first_byte : 0;
+                    items[i].in_offset = count ? src->encoded_offset + first_byte : 0;
+                    items[i].first_bit = count ? (uint8_t)(from % 8) : 0;
+                    items[i].out_capacity = count ? (hi < src->stream_symbols ? hi : src->stream_symbols) - lo : 0;
+                }
+            }
+        }
+        free(ranges);
+        free(index);
     } else {
         struct hufd_enc_item *ei = malloc((n_items ? n_items : 1) * sizeof(*ei));
         struct hufd_enc_result *er = malloc((n_items ? n_items : 1) * sizeof(*er));
@@ -2456,6 +2490,108 @@ int aws_huffman_amd_decode_plan_reset_packed_input(
     src.packed_offsets = device_offsets;
     src.packed_lengths = device_lengths;
     return dec_plan_fill_on_device(p, &src, item_count, stream);
+}
+
+/* ------------------------------------------------------------------ block index and range plans (huffman_amd_index.h) */
+
+_Static_assert(AWS_HUFFMAN_AMD_INDEX_OK == HUFK_INDEX_OK, "index status");
+_Static_assert(AWS_HUFFMAN_AMD_INDEX_SYMBOL_WITHOUT_CODE == HUFK_INDEX_SYMBOL_WITHOUT_CODE, "index status");
+_Static_assert(sizeof(struct aws_huffman_amd_block_range) == sizeof(struct hufd_block_range), "block range layout");
+_Static_assert(offsetof(struct aws_huffman_amd_block_range, block_count) == offsetof(struct hufd_block_range, block_count), "block range layout");
+_Static_assert(offsetof(struct aws_huffman_amd_block_range, out_offset) == offsetof(struct hufd_block_range, out_offset), "block range layout");
+
+static uint32_t s_index_tile_blocks = 0;
+
+void aws_huffman_amd_testing_set_index_tile_blocks(uint32_t blocks) {
+    __atomic_store_n(&s_index_tile_blocks, blocks, __ATOMIC_RELAXED);
+}
+
+static bool index_block_symbols_ok(uint64_t block_symbols) {
+    return block_symbols >= 64 && block_symbols <= (1ull << 24) && block_symbols % 64 == 0;
+}
+
+int aws_huffman_amd_block_index(
+    struct aws_huffman_amd_engine *eng,
+    const void *device_input,
+    uint64_t length,
+    uint64_t block_symbols,
+    uint64_t *device_index,
+    uint32_t *device_status,
+    void *stream) {
+
+    if (hufs_device_count() <= 0) {
+        return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION); /* no GPU: there is no CPU path */
+    }
+    if (!eng || !device_index || ((uintptr_t)device_index & 7u) || ((uintptr_t)device_status & 3u) ||
+        !index_block_symbols_ok(block_symbols) || (length && !device_input)) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    const uint64_t n_blocks = (length + block_symbols - 1) / block_symbols;
+    if (n_blocks > 0xFFFFFFFFull) { /* (the scan numbers blocks in 32 bits: 256 GiB of symbols in blocks of 64) */
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    if (engine_never_fitted(eng)) {
+        return aws_raise_error(AWS_ERROR_INVALID_STATE);
+    }
+    ON_DEVICE(eng->device);
+    pthread_mutex_lock(&eng->spare_lock);
+    if (!eng->d_index_tile_sums) { /* (the engine's first call: an allocation, so not inside a graph capture) */
+        eng->d_index_tile_sums = hufs_malloc(2 * (size_t)HUFK_INDEX_MAX_TILES * sizeof(uint64_t));
+    }
+    uint64_t *tile_sums = eng->d_index_tile_sums;
+    pthread_mutex_unlock(&eng->spare_lock);
+    if (!tile_sums) {
+        return raise_hip(2);
+    }
+    void *st = stream ? stream : eng->stream;
+    int err;
+    if (length == 0) { /* (no block, no launch: index[0] = 0 and the status, two memset nodes) */
+        err = hufs_memset(device_index, 0, sizeof(uint64_t), st);
+        if (!err && device_status) {
+            err = hufs_memset(device_status, 0, sizeof(uint32_t), st);
+        }
+    } else {
+        const uint32_t tile_blocks = hufk_index_tile_blocks((uint32_t)n_blocks, __atomic_load_n(&s_index_tile_blocks, __ATOMIC_RELAXED));
+        err = hufk_block_index(eng->d_enc_table, device_input, length, block_symbols, tile_blocks, device_index, tile_sums, device_status, st);
+    }
+    return err ? raise_hip(err) : AWS_OP_SUCCESS;
+}
+
+int aws_huffman_amd_decode_plan_reset_block_ranges(
+    struct aws_huffman_amd_decode_plan *p,
+    const uint64_t *device_index,
+    uint64_t length,
+    uint64_t block_symbols,
+    uint64_t encoded_offset,
+    uint64_t encoded_length,
+    const struct aws_huffman_amd_block_range *device_ranges,
+    size_t range_count,
+    void *stream) {
+
+    if (hufs_device_count() <= 0) {
+        return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION);
+    }
+    if (!p) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    struct hufd_item_source src;
+    memset(&src, 0, sizeof(src));
+    src.kind = HUFD_ITEMS_BLOCK_RANGES;
+    if (!device_index || ((uintptr_t)device_index & 7u) || (!device_ranges && range_count) || ((uintptr_t)device_ranges & 7u) ||
+        !index_block_symbols_ok(block_symbols)) {
+        const int rc = dec_plan_fill_on_device(p, &src, 0, stream); /* (a plan without items, as a refused range leaves it) */
+        return rc ? rc : aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    /* the planner reads the ranges and the two index entries at each range's ends where it reads any item's record: a
+     * refused range is its statistics pass's `invalid`, which comes back with the totals */
+    src.block_index = device_index;
+    src.block_ranges = (const struct hufd_block_range *)device_ranges;
+    src.n_blocks = (length + block_symbols - 1) / block_symbols;
+    src.stream_symbols = length;
+    src.block_symbols = block_symbols;
+    src.encoded_offset = encoded_offset;
+    src.encoded_length = encoded_length;
+    return dec_plan_fill_on_device(p, &src, range_count, stream);
 }
 
 /*

@@ -62,6 +62,9 @@ struct aws_huffman_amd_engine {
     struct aws_huffman_amd_encode_plan *spare_enc;
     struct aws_huffman_amd_decode_plan *spare_dec;
     bool retiring; /* the engine is being destroyed: plans are freed, not kept */
+    /* aws_huffman_amd_block_index (huffman_amd_index.h): the tile sums of its scan, 2 * HUFK_INDEX_MAX_TILES words made by the
+     * engine's first call (under spare_lock) */
+    uint64_t *d_index_tile_sums;
 };
 
 struct aws_huffman_amd_encode_plan {
