@@ -408,6 +408,8 @@ struct lane_memo {
     }
 };
 
+#include "decode_locate_body.inc"
+
 template <bool DEEP>
 __global__ __launch_bounds__(kDeepThreads) void dec_deep_kernel(
     hufd_tables tb,
@@ -419,8 +421,13 @@ __global__ __launch_bounds__(kDeepThreads) void dec_deep_kernel(
     hufd_dec_item_state *states,
     hufd_dec_result *results,
     u64 wide_from,   /* gate == NULL: items of at least this many bytes are not this launch's (dec_wide_* take them) */
-    const u32 *gate) /* != NULL: one such item after all, if dec_wide_* gave it up (the word is their ctl[0]) */ {
+    const u32 *gate, /* != NULL: one such item after all, if dec_wide_* gave it up (the word is their ctl[0]) */
+    hufd_locate loc) /* bits != NULL: the launch locates symbols of an indexed stream (decode_locate_body.inc) and decodes nothing */ {
 
+    if (loc.bits) {
+        locate_body<DEEP>(tb, loc);
+        return;
+    }
     if (gate ? gate[0] == 0 : items[deep_items[blockIdx.x]].in_len >= wide_from) {
         return;
     }
@@ -1590,7 +1597,7 @@ void hufk_host::decode_items_stage(const struct hufk_decode_args *a, hipStream_t
         const uint64_t wide_from = a->n_wide ? a->wide_from : ~0ull;
         hipLaunchKernelGGL(
             dec_deep_kernel<true>, dim3(a->n_deep), dim3(kDeepThreads), deep_lds, st, a->tables, a->items, a->deep_items,
-            kDeepLaneBytes, (const u8 *)a->d_in, (u8 *)a->d_out, a->states, a->results, wide_from, (const u32 *)nullptr);
+            kDeepLaneBytes, (const u8 *)a->d_in, (u8 *)a->d_out, a->states, a->results, wide_from, (const u32 *)nullptr, hufd_locate{});
         /* the long ones across the chip (dec_wide_*), each with dec_deep behind it in case they give it up */
         for (uint32_t k = 0; k < a->n_wide; ++k) {
             const u32 *the_item = a->deep_items + a->wide[k].slot;
@@ -1624,13 +1631,13 @@ void hufk_host::decode_items_stage(const struct hufk_decode_args *a, hipStream_t
                 (const u8 *)a->d_in, (u8 *)a->d_out, blk, a->results);
             hipLaunchKernelGGL(
                 dec_deep_kernel<true>, dim3(1), dim3(kDeepThreads), deep_lds, st, a->tables, a->items, the_item, kDeepLaneBytes,
-                (const u8 *)a->d_in, (u8 *)a->d_out, a->states, a->results, 0ull, (const u32 *)(blk + lay.ctl));
+                (const u8 *)a->d_in, (u8 *)a->d_out, a->states, a->results, 0ull, (const u32 *)(blk + lay.ctl), hufd_locate{});
         }
     } else if (a->n_deep) {
         hipLaunchKernelGGL(
             dec_deep_kernel<false>, dim3(a->n_deep), dim3(kCoopThreads), sizeof(deep_shared) + (1u << a->tables.lut_bits) * sizeof(u16),
             st, a->tables, a->items, a->deep_items, 0u, (const u8 *)a->d_in, (u8 *)a->d_out, a->states, a->results, ~0ull,
-            (const u32 *)nullptr);
+            (const u32 *)nullptr, hufd_locate{});
     }
     if (a->n_fixed_blocks && a->tables.fixed_bits) {
         /* (the items' state words start as "no symbol without a code": dec_fixed_check takes a minimum in them; the other
@@ -1683,6 +1690,35 @@ int hufk_decode_one_block(
     return (int)hipGetLastError();
 }
 
+int hufk_locate_symbols(const struct hufd_tables *tables, const struct hufd_locate *job, uint32_t walks_coop, void *stream) {
+    /* (a grid holds fewer than 2^31 workgroups: a workgroup a position takes the positions 2^30 at a time) */
+    constexpr uint64_t kStep = 1ull << 30;
+    for (uint32_t coop = 0; coop <= (walks_coop ? 1u : 0u); ++coop) {
+        const uint64_t per = coop ? 1 : kDeepThreads;
+        for (uint64_t first = 0; first < job->count; first += kStep * per) {
+            hufd_locate loc = *job;
+            loc.first = first;
+            loc.coop = coop;
+            const uint64_t left = job->count - first;
+            const uint32_t blocks = (uint32_t)(left < kStep * per ? (left + per - 1) / per : kStep);
+            loc.count = first + (left < kStep * per ? left : kStep * per);
+            if (tables->deep_entries) {
+                hipLaunchKernelGGL(
+                    dec_deep_kernel<true>, dim3(blocks), dim3(kDeepThreads), sizeof(deep_shared) + tables->deep_entries * sizeof(u32),
+                    (hipStream_t)stream, *tables, (const hufd_dec_item *)nullptr, (const u32 *)nullptr, 0u, (const u8 *)nullptr,
+                    (u8 *)nullptr, (hufd_dec_item_state *)nullptr, (hufd_dec_result *)nullptr, 0ull, (const u32 *)nullptr, loc);
+            } else {
+                hipLaunchKernelGGL(
+                    dec_deep_kernel<false>, dim3(blocks), dim3(kDeepThreads),
+                    sizeof(deep_shared) + (1u << tables->lut_bits) * sizeof(u16), (hipStream_t)stream, *tables,
+                    (const hufd_dec_item *)nullptr, (const u32 *)nullptr, 0u, (const u8 *)nullptr, (u8 *)nullptr,
+                    (hufd_dec_item_state *)nullptr, (hufd_dec_result *)nullptr, 0ull, (const u32 *)nullptr, loc);
+            }
+        }
+    }
+    return (int)hipGetLastError();
+}
+
 int hufk_decode_one_coop(
     const struct hufd_tables *tables, const struct hufd_dec_item *item, const uint32_t *zero, const void *d_in, void *d_out,
     struct hufd_dec_item_state *state, struct hufd_dec_result *result, void *stream) {
@@ -1690,13 +1726,13 @@ int hufk_decode_one_coop(
         hipLaunchKernelGGL(
             dec_deep_kernel<true>, dim3(1), dim3(kDeepThreads), sizeof(deep_shared) + tables->deep_entries * sizeof(u32),
             (hipStream_t)stream, *tables, item, zero, kDeepLaneBytes, (const u8 *)d_in, (u8 *)d_out, state, result, ~0ull,
-            (const u32 *)nullptr);
+            (const u32 *)nullptr, hufd_locate{});
     } else {
         /* (one wave: the lanes share the item evenly) */
         hipLaunchKernelGGL(
             dec_deep_kernel<false>, dim3(1), dim3(kCoopThreads),
             sizeof(deep_shared) + (1u << tables->lut_bits) * sizeof(u16), (hipStream_t)stream, *tables, item, zero, 0u,
-            (const u8 *)d_in, (u8 *)d_out, state, result, ~0ull, (const u32 *)nullptr);
+            (const u8 *)d_in, (u8 *)d_out, state, result, ~0ull, (const u32 *)nullptr, hufd_locate{});
     }
     return (int)hipGetLastError();
 }

@@ -227,12 +227,20 @@ struct hufd_chunk_rec {
 #define HUFD_ITEMS_FROM_ENCODE 2u
 #define HUFD_ITEMS_PACKED_INPUT 3u
 #define HUFD_ITEMS_BLOCK_RANGES 4u
+#define HUFD_ITEMS_SYMBOL_RANGES 5u
 /* a range of whole blocks of an indexed stream, as the public header lays it out (struct aws_huffman_amd_block_range) */
 struct hufd_block_range {
     uint64_t first_block;
     uint64_t block_count;
     uint64_t out_offset;
 };
+/* a range of symbols of an indexed stream (struct aws_huffman_amd_symbol_range, huffman_amd_ranges.h) */
+struct hufd_symbol_range {
+    uint64_t first_symbol;
+    uint64_t symbol_count;
+    uint64_t out_offset;
+};
+#define HUFD_NO_BIT 0xFFFFFFFFFFFFFFFFull /* a symbol's bit that the locate walk did not find */
 struct hufd_item_source {
     uint32_t kind;
     uint32_t first_bit;   /* strided, decode */
@@ -254,6 +262,33 @@ struct hufd_item_source {
     const uint64_t *block_index;
     const struct hufd_block_range *block_ranges;
     uint64_t n_blocks, stream_symbols, block_symbols, encoded_offset, encoded_length;
+    /* ranges of symbols of such a stream (decode, huffman_amd_ranges.h): item i is symbol_ranges[i], whose first symbol
+     * starts at bit located_bits[2 i] and whose end lies at bit located_bits[2 i + 1] (HUFD_NO_BIT: not found), as the locate
+     * body left them in front of the planner's passes; stream_symbols, encoded_offset and encoded_length as above */
+    const struct hufd_symbol_range *symbol_ranges;
+    const uint64_t *located_bits;
+};
+
+/*
+ * What a launch of the locate body is given (locate_body.hpp, hosted by dec_deep_kernel; bits == NULL: the launch decodes).
+ * Position i in [first, count) is symbols[i], or -- ranges != NULL -- an end of ranges[i / 2]: its first symbol (i even) or
+ * first_symbol + symbol_count (i odd).  bits[i] = the bit that symbol starts at in the encoded_length bytes at `encoded`,
+ * whose block k of block_symbols symbols starts at bit index[k] (n_blocks + 1 entries), or HUFD_NO_BIT with bit 0 of *status
+ * raised.  coop 0: a lane a position, for the positions at most lone_symbols codes behind their block's first; coop 1: a
+ * workgroup a position, for the others.
+ */
+struct hufd_locate {
+    const uint8_t *encoded;
+    uint64_t encoded_length;
+    const uint64_t *index;
+    uint64_t length, block_symbols, n_blocks;
+    const uint64_t *symbols;
+    const struct hufd_symbol_range *ranges;
+    uint64_t first, count;
+    uint64_t *bits;
+    uint32_t *status; /* NULL: not wanted */
+    uint32_t lone_symbols;
+    uint32_t coop;
 };
 
 #endif /* HUFFMAN_AMD_DEVICE_TYPES_H */

@@ -270,6 +270,12 @@ int hufk_block_bits(
     const uint64_t *enc_table, const void *input, uint64_t length, uint64_t block_symbols, uint64_t *index, void *stream);
 int hufk_index_scan(uint64_t *index, uint32_t n_blocks, uint32_t tile_blocks, uint64_t *tile_sums, uint32_t *status, void *stream);
 
+/* Where symbols of an indexed stream start (decode_locate_body.inc, huffman_amd_ranges.h): job->bits[i] for the positions
+ * [0, job->count) of `job` (its `first` and `coop` are the launches' own), under the decode tables of `tables`.  One launch
+ * of a lane a position; walks_coop != 0: a second of a workgroup a position, for the positions more than job->lone_symbols
+ * codes behind their block's first.  *job->status is ORed into: the caller clears it in front. */
+int hufk_locate_symbols(const struct hufd_tables *tables, const struct hufd_locate *job, uint32_t walks_coop, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -108,6 +108,31 @@ __device__ __forceinline__ raw_item load_item(const hufd_item_source &src, u32 i
                 }
             }
         }
+    } else if (!ENC && src.kind == HUFD_ITEMS_SYMBOL_RANGES) {
+        /* item i = symbols [s0, s1) of an indexed stream, whose ends the locate body found in front of this pass: from the byte
+         * that holds bit(s0) to the one that holds bit(s1) - 1, entered inside its first byte, with room for the range's
+         * symbols and no more.  A range past the stream's last symbol, an end that was not found, ends that decrease or lie
+         * behind the stream's bytes: no item */
+        const hufd_symbol_range g = src.symbol_ranges[i];
+        r.in_off = 0;
+        r.in_len = 0;
+        r.out_off = g.out_offset;
+        r.out_cap = 0;
+        r.bits = 0;
+        r.bad = 1;
+        if (g.first_symbol <= src.stream_symbols && g.symbol_count <= src.stream_symbols - g.first_symbol) {
+            const u64 from = src.located_bits[2 * (u64)i], to = src.located_bits[2 * (u64)i + 1];
+            const u64 first_byte = from / 8, end_byte = to / 8 + (to % 8 ? 1 : 0);
+            if (from != HUFD_NO_BIT && to != HUFD_NO_BIT && to >= from && end_byte <= src.encoded_length) {
+                r.bad = 0;
+                if (g.symbol_count) { /* (none: an empty item) */
+                    r.in_off = src.encoded_offset + first_byte;
+                    r.in_len = end_byte - first_byte; /* (4 GiB or more: refused with every such item) */
+                    r.bits = (u32)(from % 8);
+                    r.out_cap = g.symbol_count;
+                }
+            }
+        }
     } else if (ENC) {
         const hufd_raw_enc_item e = reinterpret_cast<const hufd_raw_enc_item *>(src.raw)[i];
         r.in_off = e.in_offset;

@@ -11,6 +11,7 @@
 #include <aws/compression/huffman_amd_fit.h>
 #include <aws/compression/huffman_amd_index.h>
 #include <aws/compression/huffman_amd_packed.h>
+#include <aws/compression/huffman_amd_ranges.h>
 
 #include <assert.h>
 #include <stdlib.h>
@@ -2074,6 +2075,37 @@ static int dec_items_to_host(
         }
         free(ranges);
         free(index);
+    } else if (src->kind == HUFD_ITEMS_SYMBOL_RANGES) {
+        /* (load_item of plan_kernels.hip is the rule this loop restates) */
+        struct hufd_symbol_range *ranges = malloc((n_items ? n_items : 1) * sizeof(*ranges));
+        uint64_t *bits = malloc((n_items ? n_items : 1) * 2 * sizeof(*bits));
+        e = ranges && bits ? 0 : 2;
+        if (!e && n_items) {
+            e = hufs_copy_d2h(ranges, src->symbol_ranges, n_items * sizeof(*ranges), st);
+        }
+        if (!e && n_items) {
+            e = hufs_copy_d2h(bits, src->located_bits, n_items * 2 * sizeof(*bits), st);
+        }
+        if (!e) {
+            e = hufs_stream_sync(st);
+        }
+        for (size_t i = 0; i < n_items && !e; ++i) {
+            const uint64_t s0 = ranges[i].first_symbol, count = ranges[i].symbol_count;
+            items[i].out_offset = ranges[i].out_offset;
+            items[i].in_len = UINT64_MAX; /* (a length no plan takes) */
+            if (s0 <= src->stream_symbols && count <= src->stream_symbols - s0) {
+                const uint64_t from = bits[2 * i], to = bits[2 * i + 1];
+                const uint64_t first_byte = from / 8, end_byte = to / 8 + (to % 8 ? 1 : 0);
+                if (from != HUFD_NO_BIT && to != HUFD_NO_BIT && to >= from && end_byte <= src->encoded_length) {
+                    items[i].in_len = count ? end_byte - first_byte : 0;
+                    items[i].in_offset = count ? src->encoded_offset + first_byte : 0;
+                    items[i].first_bit = count ? (uint8_t)(from % 8) : 0;
+                    items[i].out_capacity = count;
+                }
+            }
+        }
+        free(ranges);
+        free(bits);
     } else {
         struct hufd_enc_item *ei = malloc((n_items ? n_items : 1) * sizeof(*ei));
         struct hufd_enc_result *er = malloc((n_items ? n_items : 1) * sizeof(*er));
@@ -2239,6 +2271,7 @@ void aws_huffman_amd_decode_plan_destroy(struct aws_huffman_amd_decode_plan *p) 
         hufs_event_destroy(p->done_event);
         hufs_free(p->d_wide_block);
         hufs_free(p->d_fixed);
+        hufs_free(p->d_range_bits);
         free(p->h_wide);
         free(p->h_items);
         free(p);
@@ -2587,6 +2620,154 @@ int aws_huffman_amd_decode_plan_reset_block_ranges(
     src.block_index = device_index;
     src.block_ranges = (const struct hufd_block_range *)device_ranges;
     src.n_blocks = (length + block_symbols - 1) / block_symbols;
+    src.stream_symbols = length;
+    src.block_symbols = block_symbols;
+    src.encoded_offset = encoded_offset;
+    src.encoded_length = encoded_length;
+    return dec_plan_fill_on_device(p, &src, range_count, stream);
+}
+
+/* ------------------------------------------------------------------ symbols of an indexed stream (huffman_amd_ranges.h) */
+
+_Static_assert(AWS_HUFFMAN_AMD_NO_BIT == HUFD_NO_BIT, "no bit");
+_Static_assert(sizeof(struct aws_huffman_amd_symbol_range) == sizeof(struct hufd_symbol_range), "symbol range layout");
+_Static_assert(offsetof(struct aws_huffman_amd_symbol_range, symbol_count) == offsetof(struct hufd_symbol_range, symbol_count), "symbol range layout");
+_Static_assert(offsetof(struct aws_huffman_amd_symbol_range, out_offset) == offsetof(struct hufd_symbol_range, out_offset), "symbol range layout");
+
+/* A lane alone walks a position that is at most this many codes behind its block's first; a workgroup takes the others.
+ * profiles/symbol_ranges_mi355x.json: for 65 536 positions the two roads cross near 2 600 codes; at 512 the lone lane is six
+ * times faster ("Symbols of an indexed stream"). */
+#define LOCATE_LONE_SYMBOLS 1024u
+
+static uint32_t s_locate_lone_symbols = 0;
+
+void aws_huffman_amd_testing_set_locate_lone_symbols(uint32_t symbols) {
+    __atomic_store_n(&s_locate_lone_symbols, symbols, __ATOMIC_RELAXED);
+}
+
+/* the locate launches (and the memset that clears the status in front of them) on `st`: nothing waited for */
+static int locate_enqueue(
+    struct aws_huffman_amd_engine *eng, const void *encoded, uint64_t encoded_length, const uint64_t *index, uint64_t length,
+    uint64_t block_symbols, const uint64_t *symbols, const struct hufd_symbol_range *ranges, uint64_t count, uint64_t *bits,
+    uint32_t *status, void *st) {
+    struct hufd_locate job;
+    memset(&job, 0, sizeof(job));
+    job.encoded = encoded;
+    job.encoded_length = encoded_length;
+    job.index = index;
+    job.length = length;
+    job.block_symbols = block_symbols;
+    job.n_blocks = (length + block_symbols - 1) / block_symbols;
+    job.symbols = symbols;
+    job.ranges = ranges;
+    job.count = count;
+    job.bits = bits;
+    job.status = status;
+    const uint32_t asked = __atomic_load_n(&s_locate_lone_symbols, __ATOMIC_RELAXED);
+    job.lone_symbols = asked ? asked : LOCATE_LONE_SYMBOLS;
+    /* (a coder of one code length needs no walk; blocks no longer than the limit have no position behind it) */
+    const uint32_t walks_coop = !eng->tables.fixed_bits && (uint64_t)job.lone_symbols + 1 < block_symbols;
+    int err = status ? hufs_memset(status, 0, sizeof(uint32_t), st) : 0;
+    if (!err && count) {
+        err = hufk_locate_symbols(&eng->tables, &job, walks_coop, st);
+    }
+    return err;
+}
+
+int aws_huffman_amd_locate_symbols(
+    struct aws_huffman_amd_engine *eng,
+    const void *device_encoded,
+    uint64_t encoded_length,
+    const uint64_t *device_index,
+    uint64_t length,
+    uint64_t block_symbols,
+    const uint64_t *device_symbols,
+    size_t count,
+    uint64_t *device_bits,
+    uint32_t *device_status,
+    void *stream) {
+
+    if (hufs_device_count() <= 0) {
+        return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION); /* no GPU: there is no CPU path */
+    }
+    if (!eng || !device_index || ((uintptr_t)device_index & 7u) || ((uintptr_t)device_status & 3u) ||
+        !index_block_symbols_ok(block_symbols) || (length && !device_encoded) ||
+        (count && (!device_symbols || !device_bits)) || ((uintptr_t)device_symbols & 7u) || ((uintptr_t)device_bits & 7u)) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    if ((length + block_symbols - 1) / block_symbols > 0xFFFFFFFFull) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    if (!eng->can_decode) {
+        return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION);
+    }
+    if (engine_never_fitted(eng)) {
+        return aws_raise_error(AWS_ERROR_INVALID_STATE);
+    }
+    ON_DEVICE(eng->device);
+    const int err = locate_enqueue(
+        eng, device_encoded, encoded_length, device_index, length, block_symbols, device_symbols, NULL, count, device_bits,
+        device_status, stream ? stream : eng->stream);
+    return err ? raise_hip(err) : AWS_OP_SUCCESS;
+}
+
+int aws_huffman_amd_decode_plan_reset_symbol_ranges(
+    struct aws_huffman_amd_decode_plan *p,
+    const void *device_input,
+    const uint64_t *device_index,
+    uint64_t length,
+    uint64_t block_symbols,
+    uint64_t encoded_offset,
+    uint64_t encoded_length,
+    const struct aws_huffman_amd_symbol_range *device_ranges,
+    size_t range_count,
+    void *stream) {
+
+    if (hufs_device_count() <= 0) {
+        return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION);
+    }
+    if (!p) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    struct aws_huffman_amd_engine *eng = p->engine;
+    if (engine_never_fitted(eng)) {
+        return aws_raise_error(AWS_ERROR_INVALID_STATE);
+    }
+    struct hufd_item_source src;
+    memset(&src, 0, sizeof(src));
+    src.kind = HUFD_ITEMS_SYMBOL_RANGES;
+    if (!device_index || ((uintptr_t)device_index & 7u) || (!device_ranges && range_count) || ((uintptr_t)device_ranges & 7u) ||
+        (!device_input && range_count) || !index_block_symbols_ok(block_symbols) ||
+        (length + block_symbols - 1) / block_symbols > 0xFFFFFFFFull || range_count >= 0xFFFFFFFFull) {
+        const int rc = dec_plan_fill_on_device(p, &src, 0, stream); /* (a plan without items, as a refused range leaves it) */
+        return rc ? rc : aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    if (!eng->can_decode) {
+        return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION);
+    }
+    /* both ends of every range are located on the caller's stream, into words the plan owns, in front of the planner's
+     * passes, which read a range and its two bits where they read any item's record: a refused range (an end that was
+     * not found among them) is the statistics pass's `invalid`, which comes back with the totals */
+    if (range_count) {
+        ON_DEVICE(eng->device);
+        if (2 * range_count > p->cap_range_bits) {
+            hufs_free(p->d_range_bits);
+            p->d_range_bits = hufs_malloc(2 * range_count * sizeof(uint64_t));
+            p->cap_range_bits = p->d_range_bits ? 2 * range_count : 0;
+        }
+        if (!p->d_range_bits) {
+            return raise_hip(2);
+        }
+        const int err = locate_enqueue(
+            eng, (const uint8_t *)device_input + encoded_offset, encoded_length, device_index, length, block_symbols, NULL,
+            (const struct hufd_symbol_range *)device_ranges, 2 * (uint64_t)range_count, p->d_range_bits, NULL,
+            stream ? stream : eng->stream);
+        if (err) {
+            return raise_hip(err);
+        }
+    }
+    src.symbol_ranges = (const struct hufd_symbol_range *)device_ranges;
+    src.located_bits = p->d_range_bits;
     src.stream_symbols = length;
     src.block_symbols = block_symbols;
     src.encoded_offset = encoded_offset;

@@ -157,6 +157,8 @@ struct aws_huffman_amd_decode_plan {
     void *done_event; /* recorded behind every launch on a caller's stream: what a new plan on this one's arrays waits for */
     bool done_on_engine_stream; /* ... a launch on the engine's own stream: that stream is waited for */
     bool unkeepable;  /* not to be kept as the engine's spare (waiting for its last launch failed) */
+    uint64_t *d_range_bits; /* aws_huffman_amd_decode_plan_reset_symbol_ranges: the bits its ranges' ends were located at, two a range */
+    size_t cap_range_bits;  /* ... words */
     bool chained; /* made on the device (from an encode plan's records, a stride, or items in device memory): the items are known there only (h_items is not filled) */
     struct hufd_dec_item_state *d_states;
     uint32_t *d_summary; /* [HUFK_DEC_COUNTERS] of the last launch, as its last kernel left them: 256 bytes in front of d_results */
