@@ -55,8 +55,10 @@ inline void stage_mark(void **events, int index, hipStream_t st) {
 
 constexpr uint32_t kBesideMinChunks = 1024; /* launches of fewer chunks keep to one stream */
 
-/* a FEW chunks that streams end in among many inside streams (one long stream: one): they are workgroups of the big
- * kernels' own grids (dec_sync_one_mixed_kernel, dec_emit_fast_mixed_kernel), not launches of their own */
+/* a FEW chunks that streams end in among many inside streams (one long stream: one): in the SYNC stage they are workgroups
+ * of the big kernel's own grid (dec_sync_one_mixed_kernel), not launches of their own.  The emit stage does not fold: it
+ * forks to the side stream for dec_emit_fast<TAIL>, dec_emit_pack and dec_emit_tail as for any plan -- so 64 or more narrow
+ * folded ends pair the folded sync with the packed emit */
 inline bool tails_are_folded(const struct hufk_decode_args *a) {
     return a->n_tail && a->n_tail < a->n_chunks && (uint64_t)a->n_tail * 8 <= a->n_chunks && !a->tails_apart;
 }

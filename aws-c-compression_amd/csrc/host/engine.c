@@ -1639,6 +1639,9 @@ static int dec_plan_reserve(struct aws_huffman_amd_decode_plan *p, size_t n_item
         p->cap_runs = cr;
         /* the list counters start out clear; from then on every launch clears them for itself and for the one behind it (hufk_decode_args.counters) */
         int e = hufs_memset(p->d_counters, 0, HUFK_DEC_COUNTERS * sizeof(uint32_t), p->engine->stream);
+        if (!e) { /* (... and what a fetch reads of the last launch's lists, before any launch: nothing listed, nothing known) */
+            e = hufs_memset(p->d_summary, 0, DEC_SUMMARY_BYTES, p->engine->stream);
+        }
         if (!e) {
             e = hufs_stream_sync(p->engine->stream);
         }
@@ -1667,6 +1670,7 @@ static int dec_plan_fill(
     /* a failed refill must not leave counts of the fill before behind (the device arrays may be gone or too small) */
     p->n_items = p->n_chunks = p->n_large = p->n_runs = p->n_tail = p->n_fixed = p->n_wide = 0;
     p->quiet = false; /* (other items: nothing is known of what their launches list) */
+    p->launches_with_chunks = 0; /* (... and no launch of these has left a summary to read it from) */
     p->packed = p->packed_sized = false;
     p->longest_in_len = 0;
     p->n_tiny = p->n_deep = 0;
@@ -2157,6 +2161,7 @@ static int dec_plan_fill_on_device(struct aws_huffman_amd_decode_plan *p, const 
     }
     p->n_items = p->n_chunks = p->n_large = p->n_runs = p->n_tail = p->n_fixed = p->n_wide = 0;
     p->quiet = false; /* (other items: nothing is known of what their launches list) */
+    p->launches_with_chunks = 0; /* (... and no launch of these has left a summary to read it from) */
     p->packed = p->packed_sized = false;
     p->longest_in_len = 0;
     p->n_tiny = p->n_deep = 0;
@@ -2332,9 +2337,6 @@ static void dec_plan_launch_args(
     a.dense_list = p->d_dense_list + 1;
     a.counters = p->d_counters;
     a.counters_self_cleared = 1;
-    if (p->n_chunks) {
-        ++p->launches_with_chunks;
-    }
     a.summary = p->d_summary;
     a.quiet = p->quiet && !(testing_decode_road() & AWS_HUFFMAN_AMD_TEST_DECODE_ALL_KERNELS);
     a.lane_count = p->d_lane_count;
@@ -2377,6 +2379,9 @@ int aws_huffman_amd_decode_plan_launch_staged(
     p->packed = false; /* (the results are results for the plan's own capacities) */
     ON_DEVICE(p->engine->device);
     int err = hufk_decode_launch(&a, stream ? stream : p->engine->stream);
+    if (!err && p->n_chunks) {
+        ++p->launches_with_chunks; /* (queued whole: its last kernel leaves the lists' lengths in d_summary) */
+    }
     if (!err) {
         err = plan_mark_done(&p->done_event, &p->done_on_engine_stream, p->engine, stream);
     }
@@ -2468,6 +2473,9 @@ int aws_huffman_amd_decode_plan_launch_packed(
     struct hufk_decode_args a;
     dec_plan_launch_args(p, &a, device_input, device_output, NULL);
     err = hufk_decode_launch_packed(&a, &pk, st);
+    if (!err && p->n_chunks) {
+        ++p->launches_with_chunks;
+    }
     if (!err) {
         err = plan_mark_done(&p->done_event, &p->done_on_engine_stream, p->engine, stream);
     }
@@ -2514,7 +2522,12 @@ int aws_huffman_amd_decode_plan_reset_packed_input(
     size_t item_count,
     void *stream) {
 
-    if (!p || (!device_offsets && item_count) || ((uintptr_t)device_offsets & 7u) || ((uintptr_t)device_lengths & 7u)) {
+    if (!p) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    if ((!device_offsets && item_count) || ((uintptr_t)device_offsets & 7u) || ((uintptr_t)device_lengths & 7u)) {
+        p->quiet = false; /* (as a refused aws_huffman_amd_decode_plan_from_encode) */
+        p->launches_with_chunks = 0;
         return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
     }
     struct hufd_item_source src;
@@ -2892,6 +2905,8 @@ int aws_huffman_amd_decode_plan_from_encode(
         return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION);
     }
     if (!encoded || encoded->engine->device != eng->device || !encoded->launched) {
+        p->quiet = false; /* (a reset, refused or not: the plan's items stay, what is known of their launches' lists does not) */
+        p->launches_with_chunks = 0;
         return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT); /* (a plan that was never launched has no records to read lengths from) */
     }
     /* Whatever the launch produced, every item must be ONE THREAD's work for the decoder (then the plan has no chunk
@@ -2923,6 +2938,7 @@ int aws_huffman_amd_decode_plan_from_encode(
     }
     p->n_items = p->n_chunks = p->n_large = p->n_runs = p->n_tail = p->n_fixed = p->n_wide = 0;
     p->quiet = false; /* (other items: nothing is known of what their launches list) */
+    p->launches_with_chunks = 0; /* (... and no launch of these has left a summary to read it from) */
     p->packed = p->packed_sized = false;
     p->longest_in_len = 0;
     p->n_tiny = p->n_deep = 0;

@@ -301,7 +301,8 @@ int aws_huffman_amd_decode_plan_results(
  * dec_emit_big).  An ordinary stream lists nothing, and those four are then empty launches of ~4 us each.  The fetch of
  * a launch's results also brings back how many chunks it listed: none, and the plan is QUIET -- its next launches go
  * without the four, whatever they list goes the long way (the same results, a fifth of the speed for those chunks),
- * the next fetch says so and the four are back.  A plan is not quiet until a fetch has said so, and not after a reset.
+ * the next fetch says so and the four are back.  A plan is not quiet until a fetch has said so of a launch of its CURRENT
+ * items, and not after a reset, successful or refused.
  * (Diagnostics and tests; AWS_HUFFMAN_AMD_TEST_DECODE_ALL_KERNELS makes every launch queue all of them.) */
 AWS_COMPRESSION_API
 bool aws_huffman_amd_decode_plan_is_quiet(const struct aws_huffman_amd_decode_plan *plan);
@@ -345,8 +346,9 @@ struct aws_huffman_amd_plan_stats {
     uint64_t end_pieces_packed; /* decode: chunks a stream ends in that share a workgroup with others (dec_sync_pack) ... */
     uint64_t end_pieces_single; /* ... and that have one of their own */
     uint64_t empty;           /* items with nothing to do */
-    uint64_t end_pieces_folded; /* decode: chunks a stream ends in that are workgroups of the big kernels' own grids (a few among
-                                 * many chunks inside streams: one long stream's one) */
+    uint64_t end_pieces_folded; /* decode: chunks a stream ends in that are workgroups of the big SYNC kernel's own grid (a few
+                                 * among many chunks inside streams: one long stream's one); the emit stage takes them as
+                                 * any plan's: packed where they are narrow and at least 64, a workgroup each otherwise */
 };
 AWS_COMPRESSION_API
 int aws_huffman_amd_encode_plan_stats(const struct aws_huffman_amd_encode_plan *plan, struct aws_huffman_amd_plan_stats *stats);

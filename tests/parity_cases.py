@@ -967,10 +967,71 @@ def streams_out_of_step(w, n=260_000, seed=109, modes=(None, "long-way")):
     eng.close()
 
 
-def few_ends_among_many_chunks(w, n=330_000, seed=157, engine=None, modes=(None, "tails-apart")):
+def many_folded_ends(w, n=330_000, seed=159, engine=None, streams_in_batch=64, modes=(None,)):
+    """Sixty-four streams of nine chunks each (eight whole ones and a narrow end: at most 83 whole lanes): the ends are FEW
+    among the chunks (ends x 8 <= chunks), so the sync stage folds them into the big kernel's own grid
+    (dec_sync_one_mixed_kernel) -- and they are at least HUFD_DEC_PACK_MIN_CHUNKS narrow ones, so the emit stage, which does
+    not fold, takes them several to a workgroup (dec_emit_pack).  Folded sync with packed emit: no smaller batch pairs the
+    two.  Ends of 8 bytes up to 83 lanes, whole, cut inside a code, damaged in the last bytes and in front of them, short of
+    room, entered inside a byte.
+
+    No statistic shows what the emit stage chose (`end_pieces_packed` is 0 for folded ends).  It packs when at least 64 ends
+    are narrow AND two slots of its LDS stage fit 60 KiB, and the stage is sized by the most symbols ANY end can hold, a wide
+    one included: one stream with fewer than 8 bytes in its last chunk makes the chunk in front of it an end of 32 KiB, a
+    stage of 52 K, one slot, and every end goes through dec_emit_fast<TAIL> instead.  So this batch has no such stream
+    (few_ends_among_many_chunks has them), and the rule of decode_emit_kernels.hip (decode_emit_stage: epack_slots) is
+    restated below over the items and asserted to leave two slots."""
+    rng = np.random.default_rng(seed)
+    eng = engine or harness.Engine(w.product.lib, w.pcoder)
+    enc = oracle_encode(w, inputs(rng, n, "uniform"))
+    chunk, k, narrow_end = 32768, 8, 8 + 83 * 128
+    assert enc.size > (k + 1) * chunk, enc.size
+    ends = [8, 9, 135, 136, 137, 263, 264, 5000, narrow_end, narrow_end + 127] + [int(e) for e in rng.integers(8, narrow_end, streams_in_batch - 10)]
+    streams = []
+    for i, e in enumerate(ends):
+        cut = enc[:k * chunk + e].copy()
+        fb, cap = 0, n
+        if i % 8 == 3:  # damage in the stream's last bytes, or a lane or more in front of them
+            back = [3, 40, 140, 400][(i // 8) % 4]
+            if back < e:
+                cut[-back:-back + 2 if back > 2 else None] = 0xFF
+        elif i % 8 == 5:
+            cap = [n // 2, 236_000, 5][(i // 8) % 3]  # short of room: half-way, inside the last chunks, at once
+        elif i % 8 == 6:
+            cut, fb = enc[5:k * chunk + 5 + e].copy(), 3
+        streams.append((cut, fb, cap))
+    items = [dict(in_offset=i * 10 * chunk, in_len=int(s[0].size), first_bit=s[1], out_offset=i * n, out_capacity=s[2]) for i, s in enumerate(streams)]
+    probe = eng.decode_plan(items)
+    st = eng.decode_stats(probe)
+    eng.lib.aws_huffman_amd_decode_plan_destroy(probe)
+    assert len(streams) >= 64 and st["pieces"] == len(streams) * (k + 1), st
+    assert st["end_pieces_folded"] == len(streams) and st["end_pieces_packed"] == 0 and st["end_pieces_single"] == 0, st
+    # the emit stage's rule over these items: every end narrow, its slot width, and two stages within 60 KiB
+    min_bits = min(int(b) for b in w.table[1] if b)
+    stage = lanes = 0
+    for enc_i, _, cap in streams:
+        size = int(enc_i.size)
+        first_end = (size - 1) // chunk - (1 if size % chunk and size % chunk < 8 else 0)  # (fewer than 8 bytes: the chunk in front is an end too)
+        for c in range(first_end, (size - 1) // chunk + 1):
+            left = size - c * chunk
+            whole = (min(left, chunk + 8) - 8) // 128
+            assert 0 <= whole <= 83, ("an end that is not narrow", size, c, whole)
+            stage, lanes = max(stage, min(left * 8 // min_bits + 1, cap) + 32), max(lanes, whole)
+    slot_bytes = ((((stage + 255) & ~255) + 32 + 15) & ~15)
+    pack_fixed = 4 * 1024 + 4 * (256 + 4) + 4 * 4 + 2 * 4 * 16 + 512 + 16  # sizeof(emit_pack_shared<10>): the test coder's table has 10 bits
+    width = max(lanes + 2, 16)
+    assert width <= 128 and 512 // (4 * ((width + 1) // 2)) >= 2, (lanes, "no two slots of threads")
+    assert 2 * slot_bytes + pack_fixed <= 60 * 1024, (stage, slot_bytes, "no two slots of LDS: the emit stage would not pack")
+    decode_items_like_the_oracle(w, eng, w.ocoder, streams, rng, "sixty-four folded ends", modes=modes, kinds=2)
+    if engine is None:
+        eng.close()
+
+
+def few_ends_among_many_chunks(w, n=330_000, seed=157, engine=None, modes=(None, "tails-apart"), many_folded=False):
     """Long items (nine chunks and more each): the FEW chunks such a plan's streams end in are workgroups of the big kernels'
     own grids, the stream's last symbols followed by the workgroup itself (dec_sync_one_mixed_kernel) -- "tails-apart": kernels
-    of their own, as for a plan of many such chunks.  Ends of every kind: fewer than 8 bytes in the last chunk, 8 .. 135 (one
+    of their own, as for a plan of many such chunks.  many_folded: many_folded_ends() behind it, on the same engine (sixty-four
+    narrow ends that are folded in the sync stage and packed in the emit stage).  Ends of every kind: fewer than 8 bytes in the last chunk, 8 .. 135 (one
     thread's work), a lane or two more, nearly a whole chunk, exactly a whole chunk; cut inside a code, damaged in the last
     bytes, damaged in front of them, arbitrary bytes at the end, short of room, entered inside a byte."""
     rng = np.random.default_rng(seed)
@@ -1013,6 +1074,8 @@ def few_ends_among_many_chunks(w, n=330_000, seed=157, engine=None, modes=(None,
     eng.lib.aws_huffman_amd_decode_plan_destroy(probe)
     for label, streams, kinds in batches:
         decode_items_like_the_oracle(w, eng, w.ocoder, streams, rng, label, modes=modes, kinds=kinds)
+    if many_folded:
+        many_folded_ends(w, n=n, engine=eng)
     if engine is None:
         eng.close()
 

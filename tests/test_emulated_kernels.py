@@ -103,6 +103,11 @@ def test_few_ends_among_many_chunks(world):
     pc.few_ends_among_many_chunks(world)
 
 
+def test_sixty_four_folded_ends(world):
+    """(the batch few_ends_among_many_chunks(many_folded=True) adds on the chip: folded sync with packed emit)"""
+    pc.many_folded_ends(world)
+
+
 def test_quiet_plans(world):
     pc.quiet_plans(world, n=150_000)
 

@@ -123,7 +123,7 @@ def test_streams_with_two_last_chunks(world):
 
 
 def test_few_ends_among_many_chunks(world):
-    pc.few_ends_among_many_chunks(world)
+    pc.few_ends_among_many_chunks(world, many_folded=True)
 
 
 def test_quiet_plans(world):
