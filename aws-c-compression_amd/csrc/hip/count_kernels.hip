@@ -14,7 +14,8 @@
  * (with one copy a wave, 32 lanes on one bin take turns; profiles/tools/micro/probe_counts.hip measures both layouts).
  *
  * The same kernel has a second body, chosen by a launch argument: the hot pass of the block index (index_block_bits.hpp,
- * hufk_block_bits below), which reads the same bytes the same way and looks code lengths up where this one counts.
+ * hufk_block_bits below), which reads the same bytes the same way and looks code lengths up where this one counts -- and a
+ * third, the same pass over the items of a batch (index_batch_bits, hufk_batch_block_bits).
  */
 #include "kernels_common.hpp"
 #include "index_block_bits.hpp"
@@ -60,7 +61,11 @@ __global__ __launch_bounds__(kCountThreads) void count_kernel(
     const u8 *head, u32 head_len, const uint4 *body, u64 n_vec, const u8 *tail, u32 tail_len, u64 *counts,
     u64 steps_per_flush, index_job index) {
     if (index.index) { /* (the same in every thread of the launch) */
-        index_block_bits(index);
+        if (index.items) {
+            index_batch_bits(index);
+        } else {
+            index_block_bits(index);
+        }
         return;
     }
     u32 *tab = reinterpret_cast<u32 *>(dyn_lds);
@@ -162,6 +167,39 @@ int hufk_block_bits(
     job.index = index;
     const uint32_t grid = hufk_host::persistent_grid(
         count_kernel, kCountThreads, kIndexLdsBytes, (uint32_t)(job.n_tiles < 0xFFFFFFFFull ? job.n_tiles : 0xFFFFFFFFull));
+    hipLaunchKernelGGL(
+        count_kernel, dim3(grid), dim3(kCountThreads), kIndexLdsBytes, (hipStream_t)stream, (const u8 *)nullptr, 0u,
+        (const uint4 *)nullptr, (u64)0, (const u8 *)nullptr, 0u, (u64 *)nullptr, (u64)1, job);
+    return (int)hipGetLastError();
+}
+
+uint32_t hufk_batch_tile_blocks(uint64_t block_symbols) {
+    return (uint32_t)(block_symbols < kIndexStepBytes ? kIndexStepBytes / block_symbols : 1u);
+}
+
+int hufk_batch_block_bits(const struct hufk_batch_index *batch, uint64_t most_blocks, void *stream) {
+    index_job job{};
+    job.enc_table = batch->enc_table;
+    job.in = (const u8 *)batch->input;
+    job.block_symbols = batch->block_symbols;
+    job.groups_per_block = (u32)(batch->block_symbols / 16);
+    job.tile_blocks = hufk_batch_tile_blocks(batch->block_symbols);
+    job.inverse = job.tile_blocks > 1 ? (u32)(((1ull << 32) + job.groups_per_block - 1) / job.groups_per_block) : 0u;
+    job.wave_inverse = job.groups_per_block <= 1024u ? (u32)(((1ull << 32) + job.groups_per_block - 1) / job.groups_per_block) : 0u;
+    job.index = batch->index;
+    job.items = batch->items;
+    job.directory = batch->directory;
+    job.tile_first = batch->tile_first;
+    job.wave_bytes = batch->wave_bytes;
+    job.capacity = batch->capacity;
+    job.n_items = batch->n_items;
+    /* the tiles are counted on the device: at most one a tile's blocks of what the index has room for, and a ragged one an
+     * item; the waves want a workgroup for every eight items */
+    const u64 tiles = most_blocks / job.tile_blocks + batch->n_items;
+    const u64 by_waves = ((u64)batch->n_items + kCountThreads / kWave - 1) / (kCountThreads / kWave);
+    const u64 want = tiles > by_waves ? tiles : by_waves;
+    const uint32_t grid = hufk_host::persistent_grid(
+        count_kernel, kCountThreads, kIndexLdsBytes, (uint32_t)(want < 0xFFFFFFFFull ? want : 0xFFFFFFFFull));
     hipLaunchKernelGGL(
         count_kernel, dim3(grid), dim3(kCountThreads), kIndexLdsBytes, (hipStream_t)stream, (const u8 *)nullptr, 0u,
         (const uint4 *)nullptr, (u64)0, (const u8 *)nullptr, 0u, (u64 *)nullptr, (u64)1, job);

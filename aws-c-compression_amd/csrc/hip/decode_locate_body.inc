@@ -79,7 +79,85 @@ struct locate_position {
     u32 walk;
 };
 
+/* The item arm: (item, symbol) to the absolute span of the symbol's block, bits from the packed buffer's first byte.  The
+ * single stream's rule with the entries taken relative to the item's first and moved to the item's place; every word of a
+ * received directory, index or offset array is checked before it is an address (the rows of load_item's item kinds): what
+ * fails is not found.  The walk, both of its roads and the closed form for one-length coders are the caller's as they are */
+__device__ __forceinline__ locate_position locate_item_position_of(const hufd_locate &loc, u64 i, u32 fixed_bits) {
+    u64 item, s;
+    if (loc.items == nullptr) { /* (the ends of ranges) */
+        const hufd_item_symbol_range g = loc.item_ranges[i >> 1];
+        item = g.item;
+        s = g.first_symbol;
+        if (i & 1u) {
+            s += g.symbol_count;
+            s = s < g.first_symbol ? ~0ull : s; /* (the sum overflows: past every item) */
+        }
+    } else {
+        item = loc.items[i];
+        s = loc.symbols[i];
+    }
+    locate_position p;
+    p.bit = HUFD_NO_BIT;
+    p.from = p.to = 0;
+    p.k = 0;
+    p.walk = 0;
+    if (item >= loc.item_count) {
+        return p;
+    }
+    const u64 first = loc.directory[2 * item], symbols = loc.directory[2 * item + 1], next = loc.directory[2 * item + 2];
+    const u64 blocks = symbols / loc.block_symbols + (symbols % loc.block_symbols ? 1u : 0u);
+    const u64 at = loc.offsets[item];
+    u64 bytes;
+    bool placed = true;
+    if (loc.lengths) {
+        bytes = loc.lengths[item];
+    } else {
+        const u64 behind = loc.offsets[item + 1];
+        placed = behind >= at;
+        bytes = behind - at;
+    }
+    if (next < first || next >= loc.index_entries || next - first != blocks || s > symbols || !placed || at > loc.encoded_length ||
+        bytes > loc.encoded_length - at) {
+        return p;
+    }
+    const u64 base = loc.index[first];
+    const u64 b = s / loc.block_symbols;
+    const u32 k = (u32)(s - b * loc.block_symbols);
+    const u64 x0 = loc.index[first + b]; /* (s == symbols on a block's edge: b == blocks, the item's last entry) */
+    if (x0 < base || (x0 - base + 7) / 8 > bytes) {
+        return p;
+    }
+    const u64 from = 8 * at + (x0 - base);
+    if (k == 0) {
+        p.bit = from;
+        return p;
+    }
+    const u64 x1 = loc.index[first + b + 1]; /* (k != 0: b < blocks) */
+    if (x1 < x0 || (x1 - base + 7) / 8 > bytes) {
+        return p;
+    }
+    const u64 to = 8 * at + (x1 - base);
+    if (s == symbols) { /* the end of a ragged last block: the item's last entry */
+        p.bit = to;
+        return p;
+    }
+    if (fixed_bits) {
+        const u64 bit = from + (u64)k * fixed_bits;
+        p.bit = bit <= to ? bit : HUFD_NO_BIT;
+        return p;
+    }
+    p.from = from;
+    p.to = to;
+    p.k = k;
+    p.walk = 1;
+    return p;
+}
+
 __device__ __forceinline__ locate_position locate_position_of(const hufd_locate &loc, u64 i, u32 fixed_bits) {
+    if (loc.directory) { /* (the same in every thread of the launch) */
+        return locate_item_position_of(loc, i, fixed_bits);
+    }
     u64 s;
     if (loc.ranges) {
         const hufd_symbol_range g = loc.ranges[i >> 1];

@@ -228,6 +228,8 @@ struct hufd_chunk_rec {
 #define HUFD_ITEMS_PACKED_INPUT 3u
 #define HUFD_ITEMS_BLOCK_RANGES 4u
 #define HUFD_ITEMS_SYMBOL_RANGES 5u
+#define HUFD_ITEMS_ITEM_BLOCK_RANGES 6u
+#define HUFD_ITEMS_ITEM_SYMBOL_RANGES 7u
 /* a range of whole blocks of an indexed stream, as the public header lays it out (struct aws_huffman_amd_block_range) */
 struct hufd_block_range {
     uint64_t first_block;
@@ -236,6 +238,20 @@ struct hufd_block_range {
 };
 /* a range of symbols of an indexed stream (struct aws_huffman_amd_symbol_range, huffman_amd_ranges.h) */
 struct hufd_symbol_range {
+    uint64_t first_symbol;
+    uint64_t symbol_count;
+    uint64_t out_offset;
+};
+/* a range of whole blocks of one item of an indexed batch (struct aws_huffman_amd_item_block_range, huffman_amd_batch_index.h) */
+struct hufd_item_block_range {
+    uint64_t item;
+    uint64_t first_block;
+    uint64_t block_count;
+    uint64_t out_offset;
+};
+/* a range of symbols of one item of an indexed batch (struct aws_huffman_amd_item_symbol_range) */
+struct hufd_item_symbol_range {
+    uint64_t item;
     uint64_t first_symbol;
     uint64_t symbol_count;
     uint64_t out_offset;
@@ -267,6 +283,18 @@ struct hufd_item_source {
      * body left them in front of the planner's passes; stream_symbols, encoded_offset and encoded_length as above */
     const struct hufd_symbol_range *symbol_ranges;
     const uint64_t *located_bits;
+    /* ranges of whole blocks of the items of an indexed BATCH (decode, huffman_amd_batch_index.h): item i is
+     * item_block_ranges[i].  batch_directory: batch_items + 1 records of two words, the blocks in front of an item and its
+     * symbols; block_index: index_entries entries, one running sum over the batch; item j's encoded bytes lie
+     * packed_offsets[j] behind encoded_offset and are packed_lengths[j] long (NULL: up to packed_offsets[j + 1]), inside the
+     * encoded_length bytes of the whole buffer; block_symbols as above */
+    const struct hufd_item_block_range *item_block_ranges;
+    const uint64_t *batch_directory;
+    uint64_t batch_items, index_entries;
+    /* ranges of symbols of the items of such a batch: item i is item_symbol_ranges[i], whose ends the locate body left in
+     * located_bits[2 i] and [2 i + 1] as bits from the packed buffer's first byte (HUFD_NO_BIT: not found -- also for an item
+     * whose directory records cannot be); batch_directory, batch_items, packed_offsets / packed_lengths as above */
+    const struct hufd_item_symbol_range *item_symbol_ranges;
 };
 
 /*
@@ -281,14 +309,36 @@ struct hufd_locate {
     const uint8_t *encoded;
     uint64_t encoded_length;
     const uint64_t *index;
-    uint64_t length, block_symbols, n_blocks;
+    uint64_t block_symbols;
+    /* (what only one of the two ways of addressing needs shares its words: every word of this launch argument is a scalar
+     * register the kernel holds, and 97 of them admit one workgroup a CU fewer than 96 -- measured, the locate's cooperative
+     * road 8 to 14 % slower, profiles/batch_index_mi355x.json) */
+    union {
+        uint64_t length;     /* one stream: its symbols */
+        uint64_t item_count; /* by item */
+    };
+    union {
+        uint64_t n_blocks;      /* one stream */
+        uint64_t index_entries; /* by item: the entries of the batch's index */
+    };
     const uint64_t *symbols;
-    const struct hufd_symbol_range *ranges;
+    union {
+        const struct hufd_symbol_range *ranges;           /* one stream */
+        const struct hufd_item_symbol_range *item_ranges; /* by item */
+    };
     uint64_t first, count;
     uint64_t *bits;
     uint32_t *status; /* NULL: not wanted */
     uint32_t lone_symbols;
     uint32_t coop;
+    /* positions addressed by item (directory != NULL; huffman_amd_batch_index.h): position i is symbol symbols[i] of item
+     * items[i], or an end of item_ranges[i / 2]; `index` is the batch's (one running sum), `directory` its item_count + 1
+     * records of two words, item j's bytes lie offsets[j] into the encoded_length bytes at `encoded` and are lengths[j] long
+     * (NULL: up to offsets[j + 1]); bits[i] counts from the buffer's first byte: 8 * offsets[item] + the bit inside the item */
+    const uint64_t *directory;
+    const uint64_t *items;
+    const uint64_t *offsets;
+    const uint64_t *lengths;
 };
 
 #endif /* HUFFMAN_AMD_DEVICE_TYPES_H */

@@ -270,6 +270,47 @@ int hufk_block_bits(
     const uint64_t *enc_table, const void *input, uint64_t length, uint64_t block_symbols, uint64_t *index, void *stream);
 int hufk_index_scan(uint64_t *index, uint32_t n_blocks, uint32_t tile_blocks, uint64_t *tile_sums, uint32_t *status, void *stream);
 
+/* One block index over the items of an encode plan (index_kernels.hip, huffman_amd_batch_index.h): the directory -- record i
+ * = {the blocks in front of item i, its symbols}, record n_items = {all blocks, 0}, two words each -- and index[k] = the code
+ * bits in front of global block k, one running sum over the batch.  The host knows the capacity of the index, not the
+ * blocks: every grid is sized from `capacity` and n_items, and the kernels read the counts the directory scan left.
+ *   _batch_directory   the directory, summary[0] = all blocks, tile_first[0 .. n_items] (the tiles of the hot pass in front
+ *                      of each item; not for a size query, capacity 0), and where the batch has no block or its index does
+ *                      not fit, the status (and index[0] = 0); tile_sums: 2 * hufk_pack_tiles(n_items, tile_items) words
+ *   _batch_block_bits  the hot pass (count_kernel's body, index_block_bits.hpp): items shorter than wave_bytes a wave each,
+ *                      the others in tiles of whole blocks
+ *   _batch_index_scan  hufk_index_scan over the blocks *device_blocks says, at most most_blocks of them */
+#define HUFK_INDEX_TOO_SMALL 2u
+#define HUFK_BATCH_WAVE_MAX_BYTES 65536u /* the longest item a wave takes: its groups of 16 symbols are numbered below 2^12 */
+struct hufk_batch_index {
+    const uint64_t *enc_table;
+    const struct hufd_enc_item *items; /* the plan's records: in_off and in_len are read */
+    uint32_t n_items;
+    const void *input;
+    uint64_t block_symbols;
+    uint64_t wave_bytes;       /* 1 .. HUFK_BATCH_WAVE_MAX_BYTES */
+    uint32_t pack_tile_items;  /* hufk_pack_tile_items */
+    uint32_t index_tile_asked; /* the tests' own number for hufk_index_tile_blocks (0: the rule) */
+    uint64_t *directory;       /* the caller's: 2 * (n_items + 1) words */
+    uint64_t *index;           /* the caller's: `capacity` words (NULL with capacity 0: a size query) */
+    uint64_t capacity;
+    uint32_t *status;          /* NULL: not wanted */
+    uint64_t *tile_first;      /* scratch: n_items + 1 words */
+    uint64_t *item_tile_sums;  /* scratch: 2 * hufk_pack_tiles(n_items, pack_tile_items) words */
+    uint64_t *summary;         /* [1]: all blocks */
+    uint64_t *index_tile_sums; /* scratch: 2 * HUFK_INDEX_MAX_TILES words */
+};
+int hufk_batch_block_index(const struct hufk_batch_index *job, void *stream);
+int hufk_batch_directory(
+    const struct hufd_enc_item *items, uint32_t n_items, uint32_t tile_items, uint64_t block_symbols, uint64_t wave_bytes,
+    uint64_t tile_blocks, uint64_t capacity, uint64_t *tile_sums, uint64_t *directory, uint64_t *tile_first, uint64_t *summary,
+    uint64_t *index, uint32_t *status, void *stream);
+uint32_t hufk_batch_tile_blocks(uint64_t block_symbols);
+int hufk_batch_block_bits(const struct hufk_batch_index *job, uint64_t most_blocks, void *stream);
+int hufk_batch_index_scan(
+    uint64_t *index, const uint64_t *device_blocks, uint64_t capacity, uint32_t most_blocks, uint32_t tile_blocks, uint64_t *tile_sums,
+    uint32_t *status, void *stream);
+
 /* Where symbols of an indexed stream start (decode_locate_body.inc, huffman_amd_ranges.h): job->bits[i] for the positions
  * [0, job->count) of `job` (its `first` and `coop` are the launches' own), under the decode tables of `tables`.  One launch
  * of a lane a position; walks_coop != 0: a second of a workgroup a position, for the positions more than job->lone_symbols

@@ -92,9 +92,51 @@ struct pack_decode {
 constexpr u32 kPackIndex = 2;
 constexpr u64 kPackIndexHole = 1ull << 63;
 
-__device__ __forceinline__ u64 pack_length(const void *lengths, u32 decode, u64 i) {
+/* Two more kinds, the directory of a batch's block index (aws_huffman_amd_encode_plan_block_index, huffman_amd_batch_index.h):
+ * the "lengths" are an encode plan's item records.  kPackBlocks: an item's length is its blocks, ceil(in_len / block_symbols),
+ * and what is written is the directory -- record i = {the blocks in front of item i, in_len}, record n_items = {all blocks, 0}
+ * -- with the verdict on the caller's capacity.  kPackTiles: an item's length is the tiles the hot pass cuts it into (none
+ * for an item a wave takes), and what is written is tile_first[0 .. n_items].
+ * The scan of such an index (kPackIndex) reads its entries' count from device memory -- the host knows the capacity only and
+ * sizes the grid from that: workgroups without work leave, as all do where the entries do not fit.
+ *
+ * pack_offsets_kernel sits at 80 scalar registers, the most that admits eight of its workgroups a CU, and with these kinds
+ * compiled into it (106) the scans of ALL kinds lost two of them: the single stream's index at 64 symbols a block measured
+ * 3.6 % slower (profiles/batch_index_mi355x.json, scan_kinds_inside_pack_offsets_kernel).  So the scan's bodies are
+ * templates: the two pack kernels are the builds without these kinds, as they were, and the builds with them are further
+ * bodies of unpack_records_kernel (a thread a record, nowhere near a limit), chosen by a launch argument.  What these kinds
+ * need beyond the scan's own arguments travels in a pack_batch, a member of that launch argument. */
+constexpr u32 kPackBlocks = 3;
+constexpr u32 kPackTiles = 4;
+constexpr u64 kPackMaxBlocks = 1ull << 32; /* what an item counts at most: no sum of 2^32 items overflows */
+
+struct pack_batch {
+    u64 block_symbols, tile_blocks, wave_bytes; /* kPackBlocks, kPackTiles */
+    u64 capacity;     /* kPackBlocks, and kPackIndex with a device count: the entries of the caller's index */
+    u64 *index;       /* kPackBlocks: the caller's index (index[0] = 0 is written where the batch has no block) */
+    u32 *status;      /* kPackBlocks: the caller's status word, or NULL */
+    const u64 *count; /* kPackIndex: the batch's blocks, counted on the device (NULL: n_items holds) */
+};
+
+/* whether a batch of `blocks` blocks has an index in `capacity` entries (blocks + 1 of them, blocks below 2^32) */
+__device__ __forceinline__ bool pack_batch_fits(u64 blocks, u64 capacity) {
+    return blocks < capacity && blocks < kPackMaxBlocks;
+}
+
+template <bool BATCH>
+__device__ __forceinline__ u64 pack_length(const void *lengths, u32 decode, u64 i, const pack_batch &batch) {
     if (decode == kPackIndex) {
         return reinterpret_cast<const u64 *>(lengths)[i] & ~kPackIndexHole;
+    }
+    if (BATCH && decode >= kPackBlocks) {
+        const u64 block_symbols = batch.block_symbols, tile_blocks = batch.tile_blocks, wave_bytes = batch.wave_bytes;
+        const u64 len = reinterpret_cast<const hufd_enc_item *>(lengths)[i].in_len;
+        u64 blocks = len / block_symbols + (len % block_symbols ? 1u : 0u);
+        blocks = blocks < kPackMaxBlocks ? blocks : kPackMaxBlocks;
+        if (decode == kPackBlocks) {
+            return blocks;
+        }
+        return len < wave_bytes ? 0 : (blocks + tile_blocks - 1) / tile_blocks;
     }
     return decode ? pack_decode::length(reinterpret_cast<const pack_decode::measured *>(lengths), i)
                   : pack_encode::length(reinterpret_cast<const pack_encode::measured *>(lengths), i);
@@ -105,8 +147,21 @@ __device__ __forceinline__ u64 pack_most(const void *lengths, u32 decode, u64 i,
     return decode == kPackIndex ? reinterpret_cast<const u64 *>(lengths)[i] : reserved;
 }
 
-__device__ __forceinline__ u64 pack_reserved(const void *lengths, u32 decode, u64 i, u64 align_mask) {
-    return (pack_length(lengths, decode, i) + align_mask) & ~align_mask;
+template <bool BATCH>
+__device__ __forceinline__ u64 pack_reserved(const void *lengths, u32 decode, u64 i, u64 align_mask, const pack_batch &batch) {
+    const u64 len = pack_length<BATCH>(lengths, decode, i, batch);
+    return BATCH && decode >= kPackBlocks ? len : (len + align_mask) & ~align_mask;
+}
+
+/* the entries a scan has: for the index of a batch (`count` != NULL) what the device says, 0 where there is nothing to scan
+ * (no block, or an index that does not fit) */
+template <bool BATCH>
+__device__ __forceinline__ u32 pack_counted(u32 n_items, u32 decode, const pack_batch &batch) {
+    if (!BATCH || decode != kPackIndex || batch.count == nullptr) {
+        return n_items;
+    }
+    const u64 blocks = *batch.count;
+    return pack_batch_fits(blocks, batch.capacity) ? (u32)blocks : 0u;
 }
 
 /* the workgroup's sum and maximum, in every thread; `slots`: 2 * kPackWaves words of LDS */
@@ -162,14 +217,19 @@ __device__ __forceinline__ u64 pack_block_exclusive_sum(u64 v, u64 *slots, u64 &
 }
 
 /* tile_sums[2 b] = the sum of reserved_i over tile b, tile_sums[2 b + 1] = the largest of them */
-__global__ __launch_bounds__(kPackThreads) void pack_tile_sums_kernel(
-    const void *lengths, u32 decode, u32 n_items, u32 tile_items, u64 align_mask, u64 *tile_sums) {
+template <bool BATCH>
+__device__ __forceinline__ void pack_tile_sums_body(
+    const void *lengths, u32 decode, u32 n_items, u32 tile_items, u64 align_mask, u64 *tile_sums, const pack_batch &batch) {
     u64 *slots = reinterpret_cast<u64 *>(dyn_lds);
+    n_items = pack_counted<BATCH>(n_items, decode, batch);
     const u64 lo = (u64)blockIdx.x * tile_items;
+    if (BATCH && lo >= n_items) { /* (the same in every thread; never so where the host knows the count) */
+        return;
+    }
     const u64 hi = lo + tile_items < n_items ? lo + tile_items : n_items;
     u64 sum = 0, most = 0;
     for (u64 i = lo + threadIdx.x; i < hi; i += kPackThreads) {
-        const u64 r = pack_reserved(lengths, decode, i, align_mask);
+        const u64 r = pack_reserved<BATCH>(lengths, decode, i, align_mask, batch);
         const u64 m = pack_most(lengths, decode, i, r);
         sum += r;
         most = m > most ? m : most;
@@ -182,10 +242,15 @@ __global__ __launch_bounds__(kPackThreads) void pack_tile_sums_kernel(
 }
 
 /* offsets[0 .. n_items], packed[0 .. n_items), summary[0] = the total, summary[1] = the largest reserved length */
-__global__ __launch_bounds__(kPackThreads) void pack_offsets_kernel(
+template <bool BATCH>
+__device__ __forceinline__ void pack_offsets_body(
     const void *items, const void *lengths, u32 decode, u32 n_items, u32 tile_items, u64 align_mask, u64 capacity,
-    const u64 *tile_sums, u64 *offsets, void *packed, u64 *summary) {
+    const u64 *tile_sums, u64 *offsets, void *packed, u64 *summary, const pack_batch &batch) {
     u64 *slots = reinterpret_cast<u64 *>(dyn_lds);
+    n_items = pack_counted<BATCH>(n_items, decode, batch);
+    if (BATCH && decode == kPackIndex && (u64)blockIdx.x * tile_items >= n_items) { /* (the same in every thread; only with a device count) */
+        return;
+    }
     /* where the tile starts: the sums of the tiles in front (and, for the last workgroup's sake, their maximum) */
     u64 at = 0, most = 0;
     for (u32 k = threadIdx.x; k < blockIdx.x; k += kPackThreads) {
@@ -199,7 +264,7 @@ __global__ __launch_bounds__(kPackThreads) void pack_offsets_kernel(
     u64 mine = 0; /* the largest reserved length this thread met */
     for (u64 round = lo; round < hi; round += kPackThreads) { /* (the same trips in every thread: the scan has barriers) */
         const u64 i = round + threadIdx.x;
-        const u64 reserved = i < hi ? pack_reserved(lengths, decode, i, align_mask) : 0;
+        const u64 reserved = i < hi ? pack_reserved<BATCH>(lengths, decode, i, align_mask, batch) : 0;
         const u64 marked = i < hi ? pack_most(lengths, decode, i, reserved) : 0;
         u64 total = 0;
         const u64 off = at + pack_block_exclusive_sum(reserved, slots, total);
@@ -207,22 +272,45 @@ __global__ __launch_bounds__(kPackThreads) void pack_offsets_kernel(
             if (decode == 1) {
                 pack_decode::place(
                     reinterpret_cast<const pack_decode::item *>(items) + i, reinterpret_cast<pack_decode::item *>(packed) + i, off,
-                    pack_length(lengths, decode, i), reserved, capacity);
+                    pack_length<BATCH>(lengths, decode, i, batch), reserved, capacity);
             } else if (decode == 0) {
                 pack_encode::place(
                     reinterpret_cast<const pack_encode::item *>(items) + i, reinterpret_cast<pack_encode::item *>(packed) + i, off, 0,
                     reserved, capacity);
             }
-            offsets[i] = off; /* (never clipped: what the caller would have needed) */
+            if (BATCH && decode == kPackBlocks) {
+                offsets[2 * i] = off;
+                offsets[2 * i + 1] = reinterpret_cast<const hufd_enc_item *>(lengths)[i].in_len;
+            } else {
+                offsets[i] = off; /* (never clipped: what the caller would have needed) */
+            }
             mine = marked > mine ? marked : mine;
         }
         at += total;
     }
-    if (blockIdx.x == gridDim.x - 1) {
+    /* the last workgroup -- of those that have work, where the count came from the device */
+    if (BATCH ? hi == n_items : blockIdx.x == gridDim.x - 1) {
         u64 unused = 0;
         pack_block_sum_max(unused, mine, slots + kPackWaves);
         if (threadIdx.x == 0) {
+            if (BATCH && decode == kPackBlocks) {
+                offsets[2 * (u64)n_items] = at;
+                offsets[2 * (u64)n_items + 1] = 0;
+                summary[0] = at;
+                /* a batch with blocks that fit: the scan of the index writes the status behind the hot pass */
+                const bool fits = pack_batch_fits(at, batch.capacity);
+                if (fits && at == 0) {
+                    batch.index[0] = 0;
+                }
+                if (batch.status && (!fits || at == 0)) {
+                    *batch.status = fits ? HUFK_INDEX_OK : HUFK_INDEX_TOO_SMALL;
+                }
+                return;
+            }
             offsets[n_items] = at;
+            if (BATCH && decode == kPackTiles) {
+                return;
+            }
             if (decode == kPackIndex) {
                 if (summary) { /* (the caller's status word: four bytes) */
                     *reinterpret_cast<u32 *>(summary) =
@@ -236,12 +324,46 @@ __global__ __launch_bounds__(kPackThreads) void pack_offsets_kernel(
     }
 }
 
+__global__ __launch_bounds__(kPackThreads) void pack_tile_sums_kernel(
+    const void *lengths, u32 decode, u32 n_items, u32 tile_items, u64 align_mask, u64 *tile_sums) {
+    pack_tile_sums_body<false>(lengths, decode, n_items, tile_items, align_mask, tile_sums, pack_batch{});
+}
+
+__global__ __launch_bounds__(kPackThreads) void pack_offsets_kernel(
+    const void *items, const void *lengths, u32 decode, u32 n_items, u32 tile_items, u64 align_mask, u64 capacity,
+    const u64 *tile_sums, u64 *offsets, void *packed, u64 *summary) {
+    pack_offsets_body<false>(
+        items, lengths, decode, n_items, tile_items, align_mask, capacity, tile_sums, offsets, packed, summary, pack_batch{});
+}
+
+/* what unpack_records_kernel is given where it runs a pass of the scan with the batch kinds (pass 0: it does not) */
+struct pack_scan {
+    u32 pass; /* 1: the tile sums, 2: the offsets */
+    u32 decode, n_items, tile_items;
+    const void *lengths;
+    u64 *tile_sums, *offsets, *summary;
+    pack_batch batch;
+};
+
 /* The records of a packed decode launch that are not the scan's to write, a thread each (ONE kernel for both uses):
  *   chunk_rec == nullptr   packed[i] = items[i] with no room at all, i < n: what the kernels that walk and write in one go
  *                          count against
- *   otherwise              packed_rec[c] = chunk_rec[c] with out_off / out_cap of its item's packed record, c < n */
+ *   otherwise              packed_rec[c] = chunk_rec[c] with out_off / out_cap of its item's packed record, c < n
+ * and, chosen by a launch argument that is the same in every thread, the scan's two passes with the batch kinds (above) */
 __global__ __launch_bounds__(kPackThreads) void unpack_records_kernel(
-    const hufd_dec_item *items, hufd_dec_item *packed, const hufd_chunk_rec *chunk_rec, hufd_chunk_rec *packed_rec, u32 n) {
+    const hufd_dec_item *items, hufd_dec_item *packed, const hufd_chunk_rec *chunk_rec, hufd_chunk_rec *packed_rec, u32 n,
+    pack_scan scan) {
+    if (scan.pass == 1) {
+        pack_tile_sums_body<true>(
+            scan.lengths, scan.decode, scan.n_items, scan.tile_items, 0, scan.tile_sums, scan.batch);
+        return;
+    }
+    if (scan.pass == 2) {
+        pack_offsets_body<true>(
+            nullptr, scan.lengths, scan.decode, scan.n_items, scan.tile_items, 0, 0, scan.tile_sums, scan.offsets, nullptr,
+            scan.summary, scan.batch);
+        return;
+    }
     const u32 k = blockIdx.x * kPackThreads + threadIdx.x;
     if (k >= n) {
         return;
@@ -281,6 +403,29 @@ int pack_offsets_launch(
     return (int)hipGetLastError();
 }
 
+/* the same two passes with the batch kinds: the bodies unpack_records_kernel hosts */
+int pack_batch_launch(
+    const void *lengths, uint32_t decode, uint32_t n_items, uint32_t tile_items, uint64_t *tile_sums, uint64_t *offsets,
+    uint64_t *summary, const pack_batch &batch, hipStream_t st) {
+    /* (a directory of no items is still a record, a total and a status: one workgroup) */
+    const uint32_t tiles = n_items ? hufk_pack_tiles(n_items, tile_items) : 1u;
+    pack_scan scan{};
+    scan.decode = decode;
+    scan.n_items = n_items;
+    scan.tile_items = tile_items;
+    scan.lengths = lengths;
+    scan.tile_sums = tile_sums;
+    scan.offsets = offsets;
+    scan.summary = summary;
+    scan.batch = batch;
+    for (scan.pass = tiles > 1 ? 1 : 2; scan.pass <= 2; ++scan.pass) { /* (nobody reads the last tile's sums) */
+        hipLaunchKernelGGL(
+            unpack_records_kernel, dim3(scan.pass == 1 ? tiles - 1 : tiles), dim3(kPackThreads), kPackLdsBytes, st,
+            (const hufd_dec_item *)nullptr, (hufd_dec_item *)nullptr, (const hufd_chunk_rec *)nullptr, (hufd_chunk_rec *)nullptr, 0u, scan);
+    }
+    return (int)hipGetLastError();
+}
+
 } /* namespace */
 
 extern "C" {
@@ -312,13 +457,44 @@ int hufk_index_scan(uint64_t *index, uint32_t n_blocks, uint32_t tile_blocks, ui
         (hipStream_t)stream);
 }
 
+int hufk_batch_directory(
+    const struct hufd_enc_item *items, uint32_t n_items, uint32_t tile_items, uint64_t block_symbols, uint64_t wave_bytes,
+    uint64_t tile_blocks, uint64_t capacity, uint64_t *tile_sums, uint64_t *directory, uint64_t *tile_first, uint64_t *summary,
+    uint64_t *index, uint32_t *status, void *stream) {
+    pack_batch batch{};
+    batch.block_symbols = block_symbols;
+    batch.tile_blocks = tile_blocks;
+    batch.wave_bytes = wave_bytes;
+    batch.capacity = capacity;
+    batch.index = index;
+    batch.status = status;
+    const int e = pack_batch_launch(items, kPackBlocks, n_items, tile_items, tile_sums, directory, summary, batch, (hipStream_t)stream);
+    if (e || capacity == 0 || n_items == 0) { /* (a size query, or nothing to cut into tiles) */
+        return e;
+    }
+    return pack_batch_launch(items, kPackTiles, n_items, tile_items, tile_sums, tile_first, nullptr, batch, (hipStream_t)stream);
+}
+
+int hufk_batch_index_scan(
+    uint64_t *index, const uint64_t *device_blocks, uint64_t capacity, uint32_t most_blocks, uint32_t tile_blocks, uint64_t *tile_sums,
+    uint32_t *status, void *stream) {
+    if (most_blocks == 0 || tile_blocks == 0) {
+        return 0;
+    }
+    pack_batch batch{};
+    batch.capacity = capacity;
+    batch.count = device_blocks;
+    return pack_batch_launch(
+        index, kPackIndex, most_blocks, tile_blocks, tile_sums, index, reinterpret_cast<uint64_t *>(status), batch, (hipStream_t)stream);
+}
+
 int hufk_unpack_blank(const struct hufd_dec_item *items, uint32_t n_items, struct hufd_dec_item *packed, void *stream) {
     if (n_items == 0) {
         return 0;
     }
     hipLaunchKernelGGL(
         unpack_records_kernel, dim3((n_items + kPackThreads - 1) / kPackThreads), dim3(kPackThreads), 0, (hipStream_t)stream, items, packed,
-        (const hufd_chunk_rec *)nullptr, (hufd_chunk_rec *)nullptr, n_items);
+        (const hufd_chunk_rec *)nullptr, (hufd_chunk_rec *)nullptr, n_items, pack_scan{});
     return (int)hipGetLastError();
 }
 
@@ -333,7 +509,7 @@ int hufk_unpack_offsets(
     }
     hipLaunchKernelGGL(
         unpack_records_kernel, dim3((n_chunks + kPackThreads - 1) / kPackThreads), dim3(kPackThreads), 0, (hipStream_t)stream,
-        (const hufd_dec_item *)nullptr, packed, chunk_rec, packed_rec, n_chunks);
+        (const hufd_dec_item *)nullptr, packed, chunk_rec, packed_rec, n_chunks, pack_scan{});
     return (int)hipGetLastError();
 }
 

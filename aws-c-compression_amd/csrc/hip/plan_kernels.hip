@@ -133,6 +133,90 @@ __device__ __forceinline__ raw_item load_item(const hufd_item_source &src, u32 i
                 }
             }
         }
+    } else if (!ENC && src.kind == HUFD_ITEMS_ITEM_BLOCK_RANGES) {
+        /* item i = blocks [b0, b1) of item g.item of an indexed batch: the single stream's rule with the entries taken
+         * relative to the item's first and the bytes those of the item's own place in the buffer.  Everything a received,
+         * damaged directory or index could say is checked before it is used as an address: an item that is none, records
+         * that decrease, leave the index or disagree with the item's symbols, a range past the item's blocks, entries that
+         * decrease, bits behind the item's bytes, bytes behind the buffer -- no item.  Read: the two directory records of the
+         * item, the entries at the item's first block and at the range's ends, the item's offset (and the next, or its length) */
+        const hufd_item_block_range g = src.item_block_ranges[i];
+        r.in_off = 0;
+        r.in_len = 0;
+        r.out_off = g.out_offset;
+        r.out_cap = 0;
+        r.bits = 0;
+        r.bad = 1;
+        if (g.item < src.batch_items) {
+            const u64 first = src.batch_directory[2 * g.item], symbols = src.batch_directory[2 * g.item + 1];
+            const u64 next = src.batch_directory[2 * g.item + 2];
+            const u64 blocks = symbols / src.block_symbols + (symbols % src.block_symbols ? 1u : 0u);
+            const u64 at = src.packed_offsets[g.item];
+            u64 bytes = 0;
+            bool placed = true;
+            if (src.packed_lengths) {
+                bytes = src.packed_lengths[g.item];
+            } else {
+                const u64 behind = src.packed_offsets[g.item + 1];
+                placed = behind >= at;
+                bytes = behind - at;
+            }
+            if (next >= first && next < src.index_entries && next - first == blocks && g.first_block <= blocks &&
+                g.block_count <= blocks - g.first_block && placed && at <= src.encoded_length && bytes <= src.encoded_length - at) {
+                const u64 base = src.block_index[first];
+                const u64 x0 = src.block_index[first + g.first_block], x1 = src.block_index[first + g.first_block + g.block_count];
+                const u64 from = x0 - base, to = x1 - base;
+                const u64 first_byte = from / 8, end_byte = to / 8 + (to % 8 ? 1 : 0);
+                if (x0 >= base && x1 >= x0 && end_byte <= bytes) {
+                    r.bad = 0;
+                    if (g.block_count) { /* (none: an empty item) */
+                        const u64 lo = g.first_block * src.block_symbols, hi = (g.first_block + g.block_count) * src.block_symbols;
+                        r.in_off = src.encoded_offset + at + first_byte;
+                        r.in_len = end_byte - first_byte; /* (4 GiB or more: refused with every such item) */
+                        r.bits = (u32)(from % 8);
+                        r.out_cap = (hi < symbols ? hi : symbols) - lo;
+                    }
+                }
+            }
+        }
+    } else if (!ENC && src.kind == HUFD_ITEMS_ITEM_SYMBOL_RANGES) {
+        /* item i = symbols [s0, s1) of item g.item of an indexed batch, whose ends the locate body's item arm found in front
+         * of this pass as bits from the buffer's first byte (it checked the directory, the index and the item's place: what
+         * failed there was not found).  A range past the item's symbols, an end that was not found, ends that decrease or
+         * leave the item's bytes: no item */
+        const hufd_item_symbol_range g = src.item_symbol_ranges[i];
+        r.in_off = 0;
+        r.in_len = 0;
+        r.out_off = g.out_offset;
+        r.out_cap = 0;
+        r.bits = 0;
+        r.bad = 1;
+        if (g.item < src.batch_items) {
+            const u64 symbols = src.batch_directory[2 * g.item + 1];
+            const u64 at = src.packed_offsets[g.item];
+            u64 bytes = 0;
+            bool placed = true;
+            if (src.packed_lengths) {
+                bytes = src.packed_lengths[g.item];
+            } else {
+                const u64 behind = src.packed_offsets[g.item + 1];
+                placed = behind >= at;
+                bytes = behind - at;
+            }
+            const u64 from = src.located_bits[2 * (u64)i], to = src.located_bits[2 * (u64)i + 1];
+            const u64 first_byte = from / 8, end_byte = to / 8 + (to % 8 ? 1 : 0);
+            if (g.first_symbol <= symbols && g.symbol_count <= symbols - g.first_symbol && placed && at <= src.encoded_length &&
+                bytes <= src.encoded_length - at && from != HUFD_NO_BIT && to != HUFD_NO_BIT && to >= from && first_byte >= at &&
+                end_byte <= at + bytes) {
+                r.bad = 0;
+                if (g.symbol_count) { /* (none: an empty item) */
+                    r.in_off = src.encoded_offset + first_byte;
+                    r.in_len = end_byte - first_byte; /* (4 GiB or more: refused with every such item) */
+                    r.bits = (u32)(from % 8);
+                    r.out_cap = g.symbol_count;
+                }
+            }
+        }
     } else if (ENC) {
         const hufd_raw_enc_item e = reinterpret_cast<const hufd_raw_enc_item *>(src.raw)[i];
         r.in_off = e.in_offset;

@@ -7,6 +7,7 @@
  */
 #include "engine.h"
 
+#include <aws/compression/huffman_amd_batch_index.h>
 #include <aws/compression/huffman_amd_build.h>
 #include <aws/compression/huffman_amd_fit.h>
 #include <aws/compression/huffman_amd_index.h>
@@ -858,6 +859,7 @@ static int enc_plan_fill(
     p->most_overflow_bits = stats.worst_bits;
     p->longest_in_len = stats.longest;
     p->packed = p->packed_sized = false;
+    p->block_indexed = false;
     if (n_items >= PLAN_ON_DEVICE_MIN_ITEMS && n_items < 0xFFFFFFFFull && stats.shortest >= 1 && stats.longest <= tiny_limit &&
         stats.worst_bits <= 32) {
         /* every item is one thread's work (enc_item_is_tiny): no segments, no lists to make -- the caller's records go to the
@@ -1084,6 +1086,7 @@ static int enc_plan_fill_on_device(struct aws_huffman_amd_encode_plan *p, const 
     p->most_overflow_bits = 0;
     p->longest_in_len = 0;
     p->packed = p->packed_sized = false;
+    p->block_indexed = false;
     if (n_items == 0) {
         return AWS_OP_SUCCESS;
     }
@@ -1188,6 +1191,7 @@ void aws_huffman_amd_encode_plan_destroy(struct aws_huffman_amd_encode_plan *p) 
         ON_DEVICE(eng->device);
         enc_plan_release_device(p);
         hufs_free(p->d_packed_arena);
+        hufs_free(p->d_block_index_arena);
         hufs_free(p->d_plan_scratch);
         hufs_event_destroy(p->done_event);
         free(p);
@@ -2110,6 +2114,118 @@ static int dec_items_to_host(
         }
         free(ranges);
         free(bits);
+    } else if (src->kind == HUFD_ITEMS_ITEM_BLOCK_RANGES) {
+        /* (the directory, the index and the offsets whole; load_item of plan_kernels.hip is the rule this loop restates) */
+        const size_t n_batch = (size_t)src->batch_items, n_entries = (size_t)src->index_entries;
+        const size_t n_offsets = src->packed_lengths ? n_batch : n_batch + 1;
+        struct hufd_item_block_range *ranges = malloc((n_items ? n_items : 1) * sizeof(*ranges));
+        uint64_t *dir = malloc((n_batch + 1) * 2 * sizeof(*dir));
+        uint64_t *index = malloc((n_entries ? n_entries : 1) * sizeof(*index));
+        uint64_t *at = malloc((n_offsets ? n_offsets : 1) * sizeof(*at));
+        uint64_t *len = malloc((n_batch ? n_batch : 1) * sizeof(*len));
+        e = ranges && dir && index && at && len ? 0 : 2;
+        if (!e && n_items) {
+            e = hufs_copy_d2h(ranges, src->item_block_ranges, n_items * sizeof(*ranges), st);
+        }
+        if (!e && n_items) {
+            e = hufs_copy_d2h(dir, src->batch_directory, (n_batch + 1) * 2 * sizeof(*dir), st);
+        }
+        if (!e && n_items && n_entries) {
+            e = hufs_copy_d2h(index, src->block_index, n_entries * sizeof(*index), st);
+        }
+        if (!e && n_items && n_offsets) {
+            e = hufs_copy_d2h(at, src->packed_offsets, n_offsets * sizeof(*at), st);
+        }
+        if (!e && n_items && n_batch && src->packed_lengths) {
+            e = hufs_copy_d2h(len, src->packed_lengths, n_batch * sizeof(*len), st);
+        }
+        if (!e) {
+            e = hufs_stream_sync(st);
+        }
+        for (size_t i = 0; i < n_items && !e; ++i) {
+            const uint64_t item = ranges[i].item, b0 = ranges[i].first_block, count = ranges[i].block_count;
+            items[i].out_offset = ranges[i].out_offset;
+            items[i].in_len = UINT64_MAX; /* (a length no plan takes) */
+            if (item >= src->batch_items) {
+                continue;
+            }
+            const uint64_t first = dir[2 * item], symbols = dir[2 * item + 1], next = dir[2 * item + 2];
+            const uint64_t blocks = symbols / src->block_symbols + (symbols % src->block_symbols ? 1u : 0u);
+            const uint64_t off = at[item];
+            const bool placed = src->packed_lengths || at[item + 1] >= off;
+            const uint64_t bytes = src->packed_lengths ? len[item] : at[item + 1] - off;
+            if (next >= first && next < src->index_entries && next - first == blocks && b0 <= blocks && count <= blocks - b0 && placed &&
+                off <= src->encoded_length && bytes <= src->encoded_length - off) {
+                const uint64_t base = index[first], x0 = index[first + b0], x1 = index[first + b0 + count];
+                const uint64_t from = x0 - base, to = x1 - base;
+                const uint64_t first_byte = from / 8, end_byte = to / 8 + (to % 8 ? 1 : 0);
+                if (x0 >= base && x1 >= x0 && end_byte <= bytes) {
+                    const uint64_t lo = b0 * src->block_symbols, hi = (b0 + count) * src->block_symbols;
+                    items[i].in_len = count ? end_byte - first_byte : 0;
+                    items[i].in_offset = count ? src->encoded_offset + off + first_byte : 0;
+                    items[i].first_bit = count ? (uint8_t)(from % 8) : 0;
+                    items[i].out_capacity = count ? (hi < symbols ? hi : symbols) - lo : 0;
+                }
+            }
+        }
+        free(ranges);
+        free(dir);
+        free(index);
+        free(at);
+        free(len);
+    } else if (src->kind == HUFD_ITEMS_ITEM_SYMBOL_RANGES) {
+        /* (the directory and the offsets whole; load_item of plan_kernels.hip is the rule this loop restates) */
+        const size_t n_batch = (size_t)src->batch_items;
+        const size_t n_offsets = src->packed_lengths ? n_batch : n_batch + 1;
+        struct hufd_item_symbol_range *ranges = malloc((n_items ? n_items : 1) * sizeof(*ranges));
+        uint64_t *bits = malloc((n_items ? n_items : 1) * 2 * sizeof(*bits));
+        uint64_t *dir = malloc((n_batch + 1) * 2 * sizeof(*dir));
+        uint64_t *at = malloc((n_offsets ? n_offsets : 1) * sizeof(*at));
+        uint64_t *len = malloc((n_batch ? n_batch : 1) * sizeof(*len));
+        e = ranges && bits && dir && at && len ? 0 : 2;
+        if (!e && n_items) {
+            e = hufs_copy_d2h(ranges, src->item_symbol_ranges, n_items * sizeof(*ranges), st);
+        }
+        if (!e && n_items) {
+            e = hufs_copy_d2h(bits, src->located_bits, n_items * 2 * sizeof(*bits), st);
+        }
+        if (!e && n_items) {
+            e = hufs_copy_d2h(dir, src->batch_directory, (n_batch + 1) * 2 * sizeof(*dir), st);
+        }
+        if (!e && n_items && n_offsets) {
+            e = hufs_copy_d2h(at, src->packed_offsets, n_offsets * sizeof(*at), st);
+        }
+        if (!e && n_items && n_batch && src->packed_lengths) {
+            e = hufs_copy_d2h(len, src->packed_lengths, n_batch * sizeof(*len), st);
+        }
+        if (!e) {
+            e = hufs_stream_sync(st);
+        }
+        for (size_t i = 0; i < n_items && !e; ++i) {
+            const uint64_t item = ranges[i].item, s0 = ranges[i].first_symbol, count = ranges[i].symbol_count;
+            items[i].out_offset = ranges[i].out_offset;
+            items[i].in_len = UINT64_MAX; /* (a length no plan takes) */
+            if (item >= src->batch_items) {
+                continue;
+            }
+            const uint64_t symbols = dir[2 * item + 1], off = at[item];
+            const bool placed = src->packed_lengths || at[item + 1] >= off;
+            const uint64_t bytes = src->packed_lengths ? len[item] : at[item + 1] - off;
+            const uint64_t from = bits[2 * i], to = bits[2 * i + 1];
+            const uint64_t first_byte = from / 8, end_byte = to / 8 + (to % 8 ? 1 : 0);
+            if (s0 <= symbols && count <= symbols - s0 && placed && off <= src->encoded_length && bytes <= src->encoded_length - off &&
+                from != HUFD_NO_BIT && to != HUFD_NO_BIT && to >= from && first_byte >= off && end_byte <= off + bytes) {
+                items[i].in_len = count ? end_byte - first_byte : 0;
+                items[i].in_offset = count ? src->encoded_offset + first_byte : 0;
+                items[i].first_bit = count ? (uint8_t)(from % 8) : 0;
+                items[i].out_capacity = count;
+            }
+        }
+        free(ranges);
+        free(bits);
+        free(dir);
+        free(at);
+        free(len);
     } else {
         struct hufd_enc_item *ei = malloc((n_items ? n_items : 1) * sizeof(*ei));
         struct hufd_enc_result *er = malloc((n_items ? n_items : 1) * sizeof(*er));
@@ -2603,6 +2719,131 @@ int aws_huffman_amd_block_index(
     return err ? raise_hip(err) : AWS_OP_SUCCESS;
 }
 
+/* ------------------------------------------------------------------ one index over a plan's items (huffman_amd_batch_index.h) */
+
+_Static_assert(AWS_HUFFMAN_AMD_INDEX_TOO_SMALL == HUFK_INDEX_TOO_SMALL, "index status");
+_Static_assert(sizeof(struct aws_huffman_amd_item_blocks) == 2 * sizeof(uint64_t), "directory layout");
+_Static_assert(offsetof(struct aws_huffman_amd_item_blocks, symbols) == sizeof(uint64_t), "directory layout");
+
+#define BATCH_INDEX_WAVE_BYTES 4096u /* items shorter than this are a wave's work */
+
+static uint64_t s_batch_index_wave_bytes = 0;
+
+void aws_huffman_amd_testing_set_batch_index_wave_bytes(uint64_t bytes) {
+    __atomic_store_n(&s_batch_index_wave_bytes, bytes, __ATOMIC_RELAXED);
+}
+
+/* the call's scratch for this many items and tiles of the scans over them (grown, never shrunk): an allocation, so not
+ * inside a graph capture -- the plan's first call, or one of more items */
+static int enc_plan_reserve_block_index(struct aws_huffman_amd_encode_plan *p, size_t n_items, size_t n_tiles) {
+    if (p->d_block_index_arena && n_items <= p->cap_block_index_items && n_tiles <= p->cap_block_index_tiles) {
+        return 0;
+    }
+    hufs_free(p->d_block_index_arena); /* (waits for what still reads it) */
+    p->d_block_index_arena = NULL;
+    p->cap_block_index_items = p->cap_block_index_tiles = 0;
+    const size_t ci = n_items > p->cap_items ? n_items : p->cap_items; /* as many as the plan's own array: a reset within it allocates nothing */
+    size_t total = 0;
+    const size_t at_first = arena_cut(&total, (ci + 1) * sizeof(uint64_t));
+    const size_t at_sums = arena_cut(&total, 2 * n_tiles * sizeof(uint64_t));
+    const size_t at_summary = arena_cut(&total, sizeof(uint64_t));
+    p->d_block_index_arena = hufs_malloc(total);
+    if (!p->d_block_index_arena) {
+        return 2;
+    }
+    p->d_block_index_tile_first = (void *)((uint8_t *)p->d_block_index_arena + at_first);
+    p->d_block_index_tile_sums = (void *)((uint8_t *)p->d_block_index_arena + at_sums);
+    p->d_block_index_summary = (void *)((uint8_t *)p->d_block_index_arena + at_summary);
+    p->cap_block_index_items = ci;
+    p->cap_block_index_tiles = n_tiles;
+    return 0;
+}
+
+int aws_huffman_amd_encode_plan_block_index(
+    struct aws_huffman_amd_encode_plan *p,
+    const void *device_input,
+    uint64_t block_symbols,
+    struct aws_huffman_amd_item_blocks *device_directory,
+    uint64_t *device_index,
+    uint64_t index_capacity,
+    uint32_t *device_status,
+    void *stream) {
+
+    if (hufs_device_count() <= 0) {
+        return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION); /* no GPU: there is no CPU path */
+    }
+    if (!p || !device_directory || ((uintptr_t)device_directory & 7u) || ((uintptr_t)device_index & 7u) ||
+        ((uintptr_t)device_status & 3u) || (device_index == NULL) != (index_capacity == 0) || !index_block_symbols_ok(block_symbols) ||
+        (p->n_items && !device_input)) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    struct aws_huffman_amd_engine *eng = p->engine;
+    if (engine_never_fitted(eng)) {
+        return aws_raise_error(AWS_ERROR_INVALID_STATE);
+    }
+    ON_DEVICE(eng->device);
+    pthread_mutex_lock(&eng->spare_lock);
+    if (!eng->d_index_tile_sums) { /* (as aws_huffman_amd_block_index: the engine's first call of either) */
+        eng->d_index_tile_sums = hufs_malloc(2 * (size_t)HUFK_INDEX_MAX_TILES * sizeof(uint64_t));
+    }
+    uint64_t *index_tile_sums = eng->d_index_tile_sums;
+    pthread_mutex_unlock(&eng->spare_lock);
+    if (!index_tile_sums) {
+        return raise_hip(2);
+    }
+    struct hufk_batch_index job;
+    memset(&job, 0, sizeof(job));
+    job.pack_tile_items = hufk_pack_tile_items(p->n_items, __atomic_load_n(&s_pack_tile_items, __ATOMIC_RELAXED));
+    const int reserved = enc_plan_reserve_block_index(p, p->n_items, p->n_items ? hufk_pack_tiles(p->n_items, job.pack_tile_items) : 1);
+    if (reserved) {
+        return raise_hip(reserved);
+    }
+    uint64_t wave_bytes = __atomic_load_n(&s_batch_index_wave_bytes, __ATOMIC_RELAXED);
+    wave_bytes = wave_bytes ? wave_bytes : BATCH_INDEX_WAVE_BYTES;
+    job.enc_table = eng->d_enc_table;
+    job.items = p->d_items;
+    job.n_items = p->n_items;
+    job.input = device_input;
+    job.block_symbols = block_symbols;
+    job.wave_bytes = wave_bytes < HUFK_BATCH_WAVE_MAX_BYTES ? wave_bytes : HUFK_BATCH_WAVE_MAX_BYTES;
+    job.index_tile_asked = __atomic_load_n(&s_index_tile_blocks, __ATOMIC_RELAXED);
+    job.directory = (uint64_t *)device_directory;
+    job.index = device_index;
+    job.capacity = index_capacity;
+    job.status = device_status;
+    job.tile_first = p->d_block_index_tile_first;
+    job.item_tile_sums = p->d_block_index_tile_sums;
+    job.summary = p->d_block_index_summary;
+    job.index_tile_sums = index_tile_sums;
+    int err = hufk_batch_block_index(&job, stream ? stream : eng->stream);
+    if (!err) { /* (the plan's records and scratch are read on this stream: whoever gets its arrays next waits, as for a launch) */
+        err = plan_mark_done(&p->done_event, &p->done_on_engine_stream, eng, stream);
+    }
+    if (err) {
+        return raise_hip(err);
+    }
+    p->block_indexed = true;
+    return AWS_OP_SUCCESS;
+}
+
+int aws_huffman_amd_encode_plan_block_index_size(struct aws_huffman_amd_encode_plan *p, uint64_t *entries, void *stream) {
+    if (!p || !entries || !p->block_indexed) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    uint64_t blocks = 0;
+    ON_DEVICE(p->engine->device);
+    void *st = stream ? stream : p->engine->stream;
+    int err = hufs_copy_d2h(&blocks, p->d_block_index_summary, sizeof(blocks), st);
+    if (!err) {
+        err = hufs_stream_sync(st);
+    }
+    if (err) {
+        return raise_hip(err);
+    }
+    *entries = blocks + 1;
+    return AWS_OP_SUCCESS;
+}
+
 int aws_huffman_amd_decode_plan_reset_block_ranges(
     struct aws_huffman_amd_decode_plan *p,
     const uint64_t *device_index,
@@ -2635,6 +2876,57 @@ int aws_huffman_amd_decode_plan_reset_block_ranges(
     src.n_blocks = (length + block_symbols - 1) / block_symbols;
     src.stream_symbols = length;
     src.block_symbols = block_symbols;
+    src.encoded_offset = encoded_offset;
+    src.encoded_length = encoded_length;
+    return dec_plan_fill_on_device(p, &src, range_count, stream);
+}
+
+_Static_assert(sizeof(struct aws_huffman_amd_item_block_range) == sizeof(struct hufd_item_block_range), "item block range layout");
+_Static_assert(offsetof(struct aws_huffman_amd_item_block_range, first_block) == offsetof(struct hufd_item_block_range, first_block), "item block range layout");
+_Static_assert(offsetof(struct aws_huffman_amd_item_block_range, block_count) == offsetof(struct hufd_item_block_range, block_count), "item block range layout");
+_Static_assert(offsetof(struct aws_huffman_amd_item_block_range, out_offset) == offsetof(struct hufd_item_block_range, out_offset), "item block range layout");
+
+int aws_huffman_amd_decode_plan_reset_item_block_ranges(
+    struct aws_huffman_amd_decode_plan *p,
+    const struct aws_huffman_amd_item_blocks *device_directory,
+    const uint64_t *device_index,
+    uint64_t index_entries,
+    uint64_t item_count,
+    uint64_t block_symbols,
+    const uint64_t *device_encoded_offsets,
+    const uint64_t *device_encoded_lengths,
+    uint64_t encoded_offset,
+    uint64_t encoded_length,
+    const struct aws_huffman_amd_item_block_range *device_ranges,
+    size_t range_count,
+    void *stream) {
+
+    if (hufs_device_count() <= 0) {
+        return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION);
+    }
+    if (!p) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    struct hufd_item_source src;
+    memset(&src, 0, sizeof(src));
+    src.kind = HUFD_ITEMS_ITEM_BLOCK_RANGES;
+    if (!device_directory || ((uintptr_t)device_directory & 7u) || !device_index || ((uintptr_t)device_index & 7u) || index_entries == 0 ||
+        item_count >= 0xFFFFFFFFull || !device_encoded_offsets || ((uintptr_t)device_encoded_offsets & 7u) ||
+        ((uintptr_t)device_encoded_lengths & 7u) || (!device_ranges && range_count) || ((uintptr_t)device_ranges & 7u) ||
+        !index_block_symbols_ok(block_symbols)) {
+        const int rc = dec_plan_fill_on_device(p, &src, 0, stream); /* (a plan without items, as a refused range leaves it) */
+        return rc ? rc : aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    /* the planner reads a range, its item's two directory records, place and three index entries where it reads any item's
+     * record: a refused range is its statistics pass's `invalid`, which comes back with the totals */
+    src.item_block_ranges = (const struct hufd_item_block_range *)device_ranges;
+    src.batch_directory = (const uint64_t *)device_directory;
+    src.batch_items = item_count;
+    src.block_index = device_index;
+    src.index_entries = index_entries;
+    src.block_symbols = block_symbols;
+    src.packed_offsets = device_encoded_offsets;
+    src.packed_lengths = device_encoded_lengths;
     src.encoded_offset = encoded_offset;
     src.encoded_length = encoded_length;
     return dec_plan_fill_on_device(p, &src, range_count, stream);
@@ -2783,6 +3075,169 @@ int aws_huffman_amd_decode_plan_reset_symbol_ranges(
     src.located_bits = p->d_range_bits;
     src.stream_symbols = length;
     src.block_symbols = block_symbols;
+    src.encoded_offset = encoded_offset;
+    src.encoded_length = encoded_length;
+    return dec_plan_fill_on_device(p, &src, range_count, stream);
+}
+
+/* ------------------------------------------------------------------ symbols addressed by item (huffman_amd_batch_index.h) */
+
+_Static_assert(sizeof(struct aws_huffman_amd_item_symbol_range) == sizeof(struct hufd_item_symbol_range), "item symbol range layout");
+_Static_assert(offsetof(struct aws_huffman_amd_item_symbol_range, first_symbol) == offsetof(struct hufd_item_symbol_range, first_symbol), "item symbol range layout");
+_Static_assert(offsetof(struct aws_huffman_amd_item_symbol_range, symbol_count) == offsetof(struct hufd_item_symbol_range, symbol_count), "item symbol range layout");
+_Static_assert(offsetof(struct aws_huffman_amd_item_symbol_range, out_offset) == offsetof(struct hufd_item_symbol_range, out_offset), "item symbol range layout");
+
+/* where the items of an indexed batch lie, as the three calls that address by item are told */
+struct batch_place {
+    const void *encoded; /* the packed buffer's first byte */
+    uint64_t encoded_length;
+    const uint64_t *directory, *index, *offsets, *lengths;
+    uint64_t index_entries, item_count, block_symbols;
+};
+
+static bool batch_place_ok(const struct batch_place *b) {
+    return b->directory && !((uintptr_t)b->directory & 7u) && b->index && !((uintptr_t)b->index & 7u) && b->index_entries &&
+           b->item_count < 0xFFFFFFFFull && b->offsets && !((uintptr_t)b->offsets & 7u) && !((uintptr_t)b->lengths & 7u) &&
+           index_block_symbols_ok(b->block_symbols);
+}
+
+/* locate_enqueue for positions addressed by item: items[i] / symbols[i], or the ends of ranges */
+static int locate_items_enqueue(
+    struct aws_huffman_amd_engine *eng, const struct batch_place *b, const uint64_t *items, const uint64_t *symbols,
+    const struct hufd_item_symbol_range *ranges, uint64_t count, uint64_t *bits, uint32_t *status, void *st) {
+    struct hufd_locate job;
+    memset(&job, 0, sizeof(job));
+    job.encoded = b->encoded;
+    job.encoded_length = b->encoded_length;
+    job.index = b->index;
+    job.block_symbols = b->block_symbols;
+    job.symbols = symbols;
+    job.items = items;
+    job.item_ranges = ranges;
+    job.directory = b->directory;
+    job.offsets = b->offsets;
+    job.lengths = b->lengths;
+    job.item_count = b->item_count;
+    job.index_entries = b->index_entries;
+    job.count = count;
+    job.bits = bits;
+    job.status = status;
+    const uint32_t asked = __atomic_load_n(&s_locate_lone_symbols, __ATOMIC_RELAXED);
+    job.lone_symbols = asked ? asked : LOCATE_LONE_SYMBOLS;
+    const uint32_t walks_coop = !eng->tables.fixed_bits && (uint64_t)job.lone_symbols + 1 < b->block_symbols;
+    int err = status ? hufs_memset(status, 0, sizeof(uint32_t), st) : 0;
+    if (!err && count) {
+        err = hufk_locate_symbols(&eng->tables, &job, walks_coop, st);
+    }
+    return err;
+}
+
+int aws_huffman_amd_locate_item_symbols(
+    struct aws_huffman_amd_engine *eng,
+    const void *device_encoded,
+    uint64_t encoded_length,
+    const struct aws_huffman_amd_item_blocks *device_directory,
+    const uint64_t *device_index,
+    uint64_t index_entries,
+    uint64_t item_count,
+    uint64_t block_symbols,
+    const uint64_t *device_encoded_offsets,
+    const uint64_t *device_encoded_lengths,
+    const uint64_t *device_items,
+    const uint64_t *device_symbols,
+    size_t count,
+    uint64_t *device_bits,
+    uint32_t *device_status,
+    void *stream) {
+
+    if (hufs_device_count() <= 0) {
+        return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION); /* no GPU: there is no CPU path */
+    }
+    const struct batch_place place = {device_encoded, encoded_length, (const uint64_t *)device_directory, device_index,
+                                      device_encoded_offsets, device_encoded_lengths, index_entries, item_count, block_symbols};
+    if (!eng || !batch_place_ok(&place) || ((uintptr_t)device_status & 3u) || (encoded_length && !device_encoded) ||
+        (count && (!device_items || !device_symbols || !device_bits)) || ((uintptr_t)device_items & 7u) ||
+        ((uintptr_t)device_symbols & 7u) || ((uintptr_t)device_bits & 7u)) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    if (!eng->can_decode) {
+        return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION);
+    }
+    if (engine_never_fitted(eng)) {
+        return aws_raise_error(AWS_ERROR_INVALID_STATE);
+    }
+    ON_DEVICE(eng->device);
+    const int err = locate_items_enqueue(
+        eng, &place, device_items, device_symbols, NULL, count, device_bits, device_status, stream ? stream : eng->stream);
+    return err ? raise_hip(err) : AWS_OP_SUCCESS;
+}
+
+int aws_huffman_amd_decode_plan_reset_item_symbol_ranges(
+    struct aws_huffman_amd_decode_plan *p,
+    const void *device_input,
+    const struct aws_huffman_amd_item_blocks *device_directory,
+    const uint64_t *device_index,
+    uint64_t index_entries,
+    uint64_t item_count,
+    uint64_t block_symbols,
+    const uint64_t *device_encoded_offsets,
+    const uint64_t *device_encoded_lengths,
+    uint64_t encoded_offset,
+    uint64_t encoded_length,
+    const struct aws_huffman_amd_item_symbol_range *device_ranges,
+    size_t range_count,
+    void *stream) {
+
+    if (hufs_device_count() <= 0) {
+        return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION);
+    }
+    if (!p) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    struct aws_huffman_amd_engine *eng = p->engine;
+    if (engine_never_fitted(eng)) {
+        return aws_raise_error(AWS_ERROR_INVALID_STATE);
+    }
+    struct hufd_item_source src;
+    memset(&src, 0, sizeof(src));
+    src.kind = HUFD_ITEMS_ITEM_SYMBOL_RANGES;
+    const struct batch_place place = {(const uint8_t *)device_input + encoded_offset, encoded_length, (const uint64_t *)device_directory,
+                                      device_index, device_encoded_offsets, device_encoded_lengths, index_entries, item_count,
+                                      block_symbols};
+    if (!batch_place_ok(&place) || (!device_ranges && range_count) || ((uintptr_t)device_ranges & 7u) || (!device_input && range_count) ||
+        range_count >= 0xFFFFFFFFull) {
+        const int rc = dec_plan_fill_on_device(p, &src, 0, stream); /* (a plan without items, as a refused range leaves it) */
+        return rc ? rc : aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    if (!eng->can_decode) {
+        return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION);
+    }
+    /* as aws_huffman_amd_decode_plan_reset_symbol_ranges: both ends of every range located on the caller's stream into words
+     * the plan owns, in front of the planner's passes; an end that was not found is the statistics pass's `invalid` */
+    if (range_count) {
+        ON_DEVICE(eng->device);
+        if (2 * range_count > p->cap_range_bits) {
+            hufs_free(p->d_range_bits);
+            p->d_range_bits = hufs_malloc(2 * range_count * sizeof(uint64_t));
+            p->cap_range_bits = p->d_range_bits ? 2 * range_count : 0;
+        }
+        if (!p->d_range_bits) {
+            return raise_hip(2);
+        }
+        const int err = locate_items_enqueue(
+            eng, &place, NULL, NULL, (const struct hufd_item_symbol_range *)device_ranges, 2 * (uint64_t)range_count, p->d_range_bits,
+            NULL, stream ? stream : eng->stream);
+        if (err) {
+            return raise_hip(err);
+        }
+    }
+    src.item_symbol_ranges = (const struct hufd_item_symbol_range *)device_ranges;
+    src.located_bits = p->d_range_bits;
+    src.batch_directory = (const uint64_t *)device_directory;
+    src.batch_items = item_count;
+    src.block_symbols = block_symbols;
+    src.packed_offsets = device_encoded_offsets;
+    src.packed_lengths = device_encoded_lengths;
     src.encoded_offset = encoded_offset;
     src.encoded_length = encoded_length;
     return dec_plan_fill_on_device(p, &src, range_count, stream);

@@ -118,6 +118,15 @@ struct aws_huffman_amd_encode_plan {
     size_t cap_packed_items, cap_pack_tiles;
     bool packed;       /* the last encode launch was a packed one: its output lies where d_packed_items say */
     bool packed_sized; /* ... and one was made since the plan was filled: d_pack_summary is of these items */
+    /* aws_huffman_amd_encode_plan_block_index (huffman_amd_batch_index.h): the tiles of its hot pass in front of each item,
+     * the tile sums of its two scans over the items and the word that holds all blocks; ONE allocation, made by the plan's
+     * first such call and grown by a later one of more items or tiles */
+    void *d_block_index_arena;
+    uint64_t *d_block_index_tile_first; /* [cap_block_index_items + 1] */
+    uint64_t *d_block_index_tile_sums;  /* [2 * cap_block_index_tiles] */
+    uint64_t *d_block_index_summary;    /* [1] */
+    size_t cap_block_index_items, cap_block_index_tiles;
+    bool block_indexed; /* such a call was made since the plan was filled: d_block_index_summary is of these items */
 };
 
 struct aws_huffman_amd_decode_plan {

@@ -17,9 +17,9 @@
  * The index is 8 bytes a block: 0.05 % of the symbols at 16 384 symbols a block, 12.5 % at 64.
  *
  * Ranges that start or end inside a block: huffman_amd_ranges.h (any range of symbols, located from this index on the
- * device).  Out of this interface: an index made by the encode launch itself (it would save this second read of the symbols
- * and touches the one-pass encoder), one index over many items of a plan (the stream is one item: index it item by item),
- * and aws_huffman_amd_shards_*.
+ * device).  One index over the items of a plan: huffman_amd_batch_index.h.  Out of this interface: an index made by the
+ * encode launch itself (it would save this second read of the symbols and touches the one-pass encoder), and
+ * aws_huffman_amd_shards_*.
  */
 
 #include <aws/compression/huffman_amd.h>

@@ -16,8 +16,8 @@
  * the range's ends: at most the two blocks they lie in), where a plan over the covering blocks decodes and reserves
  * 16 384.  The index stays as coarse as it is: 0.05 % of the symbols at 16 384 symbols a block.
  *
- * Out of this interface: an index made by the encode launch itself, one index over many items of a plan, and
- * aws_huffman_amd_shards_*.
+ * Out of this interface: an index made by the encode launch itself, and aws_huffman_amd_shards_* (one index over the items
+ * of a plan: huffman_amd_batch_index.h).
  */
 
 #include <aws/compression/huffman_amd_index.h>
