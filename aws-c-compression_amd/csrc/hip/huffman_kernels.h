@@ -311,6 +311,16 @@ int hufk_batch_index_scan(
     uint64_t *index, const uint64_t *device_blocks, uint64_t capacity, uint32_t most_blocks, uint32_t tile_blocks, uint64_t *tile_sums,
     uint32_t *status, void *stream);
 
+/* The offsets of a packed launch from the batch's block index in place of a length pass (pack_kernels.hip,
+ * huffman_amd_packed_index.h): behind hufk_batch_block_index on the same stream, with f_i = directory[2 i],
+ * len_i = ceil((index[f_{i+1}] - index[f_i] + items[i].ovf_bits) / 8), and offsets, packed and summary from these as
+ * hufk_pack_offsets makes them from a length pass's records.  Where the batch's blocks (directory[2 n_items]) have no index in
+ * index_capacity entries, every len_i is 0: offsets and summary all 0, packed[i] with no room. */
+int hufk_pack_offsets_indexed(
+    const struct hufd_enc_item *items, uint32_t n_items, uint32_t tile_items, uint64_t align, uint64_t capacity,
+    const uint64_t *directory, const uint64_t *index, uint64_t index_capacity, uint64_t *tile_sums, uint64_t *offsets,
+    struct hufd_enc_item *packed, uint64_t *summary, void *stream);
+
 /* Where symbols of an indexed stream start (decode_locate_body.inc, huffman_amd_ranges.h): job->bits[i] for the positions
  * [0, job->count) of `job` (its `first` and `coop` are the launches' own), under the decode tables of `tables`.  One launch
  * of a lane a position; walks_coop != 0: a second of a workgroup a position, for the positions more than job->lone_symbols

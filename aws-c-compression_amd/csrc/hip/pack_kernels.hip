@@ -108,6 +108,16 @@ constexpr u64 kPackIndexHole = 1ull << 63;
  * need beyond the scan's own arguments travels in a pack_batch, a member of that launch argument. */
 constexpr u32 kPackBlocks = 3;
 constexpr u32 kPackTiles = 4;
+/* A sixth kind, the offsets of a packed launch that has made the batch's block index in place of its length pass
+ * (aws_huffman_amd_encode_plan_launch_packed_indexed, huffman_amd_packed_index.h): the "lengths" are the plan's item records
+ * again, and an item's length is what the scanned index says of it, with f_i = directory[i].first_block
+ *   len_i = ceil((index[f_{i+1}] - index[f_i] + ovf_bits_i) / 8)
+ * -- the carried bits count towards the length, not towards the index -- rounded and placed as kind 0 does (pack_encode::place).
+ * Where the index does not fit the device has no lengths: every length is 0, so every offset, every room and both summary
+ * words are.  It lives here, not in pack_offsets_kernel, for the reason above, and as builds of the bodies of its own
+ * (INDEXED, the kind a constant in them): compiled into the builds of the other batch kinds the kernel parked sixteen scalar
+ * registers in vector lanes, with builds of its own four (no scratch memory either way). */
+constexpr u32 kPackIndexed = 5;
 constexpr u64 kPackMaxBlocks = 1ull << 32; /* what an item counts at most: no sum of 2^32 items overflows */
 
 struct pack_batch {
@@ -115,7 +125,8 @@ struct pack_batch {
     u64 capacity;     /* kPackBlocks, and kPackIndex with a device count: the entries of the caller's index */
     u64 *index;       /* kPackBlocks: the caller's index (index[0] = 0 is written where the batch has no block) */
     u32 *status;      /* kPackBlocks: the caller's status word, or NULL */
-    const u64 *count; /* kPackIndex: the batch's blocks, counted on the device (NULL: n_items holds) */
+    const u64 *count; /* kPackIndex: the batch's blocks, counted on the device (NULL: n_items holds); kPackIndexed: the same word */
+    const u64 *directory; /* kPackIndexed: [n_items + 1][2], and `index` scanned, `capacity` its entries */
 };
 
 /* whether a batch of `blocks` blocks has an index in `capacity` entries (blocks + 1 of them, blocks below 2^32) */
@@ -123,10 +134,17 @@ __device__ __forceinline__ bool pack_batch_fits(u64 blocks, u64 capacity) {
     return blocks < capacity && blocks < kPackMaxBlocks;
 }
 
-template <bool BATCH>
+template <bool BATCH, bool INDEXED = false>
 __device__ __forceinline__ u64 pack_length(const void *lengths, u32 decode, u64 i, const pack_batch &batch) {
     if (decode == kPackIndex) {
         return reinterpret_cast<const u64 *>(lengths)[i] & ~kPackIndexHole;
+    }
+    if (INDEXED) {
+        if (!pack_batch_fits(*batch.count, batch.capacity)) { /* (the same in every thread of the launch) */
+            return 0;
+        }
+        const u64 from = batch.index[batch.directory[2 * i]], to = batch.index[batch.directory[2 * i + 2]];
+        return (to - from + reinterpret_cast<const hufd_enc_item *>(lengths)[i].ovf_bits + 7) / 8;
     }
     if (BATCH && decode >= kPackBlocks) {
         const u64 block_symbols = batch.block_symbols, tile_blocks = batch.tile_blocks, wave_bytes = batch.wave_bytes;
@@ -147,10 +165,10 @@ __device__ __forceinline__ u64 pack_most(const void *lengths, u32 decode, u64 i,
     return decode == kPackIndex ? reinterpret_cast<const u64 *>(lengths)[i] : reserved;
 }
 
-template <bool BATCH>
+template <bool BATCH, bool INDEXED = false>
 __device__ __forceinline__ u64 pack_reserved(const void *lengths, u32 decode, u64 i, u64 align_mask, const pack_batch &batch) {
-    const u64 len = pack_length<BATCH>(lengths, decode, i, batch);
-    return BATCH && decode >= kPackBlocks ? len : (len + align_mask) & ~align_mask;
+    const u64 len = pack_length<BATCH, INDEXED>(lengths, decode, i, batch);
+    return BATCH && !INDEXED && decode >= kPackBlocks ? len : (len + align_mask) & ~align_mask;
 }
 
 /* the entries a scan has: for the index of a batch (`count` != NULL) what the device says, 0 where there is nothing to scan
@@ -217,7 +235,7 @@ __device__ __forceinline__ u64 pack_block_exclusive_sum(u64 v, u64 *slots, u64 &
 }
 
 /* tile_sums[2 b] = the sum of reserved_i over tile b, tile_sums[2 b + 1] = the largest of them */
-template <bool BATCH>
+template <bool BATCH, bool INDEXED = false>
 __device__ __forceinline__ void pack_tile_sums_body(
     const void *lengths, u32 decode, u32 n_items, u32 tile_items, u64 align_mask, u64 *tile_sums, const pack_batch &batch) {
     u64 *slots = reinterpret_cast<u64 *>(dyn_lds);
@@ -229,7 +247,7 @@ __device__ __forceinline__ void pack_tile_sums_body(
     const u64 hi = lo + tile_items < n_items ? lo + tile_items : n_items;
     u64 sum = 0, most = 0;
     for (u64 i = lo + threadIdx.x; i < hi; i += kPackThreads) {
-        const u64 r = pack_reserved<BATCH>(lengths, decode, i, align_mask, batch);
+        const u64 r = pack_reserved<BATCH, INDEXED>(lengths, decode, i, align_mask, batch);
         const u64 m = pack_most(lengths, decode, i, r);
         sum += r;
         most = m > most ? m : most;
@@ -242,7 +260,7 @@ __device__ __forceinline__ void pack_tile_sums_body(
 }
 
 /* offsets[0 .. n_items], packed[0 .. n_items), summary[0] = the total, summary[1] = the largest reserved length */
-template <bool BATCH>
+template <bool BATCH, bool INDEXED = false>
 __device__ __forceinline__ void pack_offsets_body(
     const void *items, const void *lengths, u32 decode, u32 n_items, u32 tile_items, u64 align_mask, u64 capacity,
     const u64 *tile_sums, u64 *offsets, void *packed, u64 *summary, const pack_batch &batch) {
@@ -264,7 +282,7 @@ __device__ __forceinline__ void pack_offsets_body(
     u64 mine = 0; /* the largest reserved length this thread met */
     for (u64 round = lo; round < hi; round += kPackThreads) { /* (the same trips in every thread: the scan has barriers) */
         const u64 i = round + threadIdx.x;
-        const u64 reserved = i < hi ? pack_reserved<BATCH>(lengths, decode, i, align_mask, batch) : 0;
+        const u64 reserved = i < hi ? pack_reserved<BATCH, INDEXED>(lengths, decode, i, align_mask, batch) : 0;
         const u64 marked = i < hi ? pack_most(lengths, decode, i, reserved) : 0;
         u64 total = 0;
         const u64 off = at + pack_block_exclusive_sum(reserved, slots, total);
@@ -273,7 +291,7 @@ __device__ __forceinline__ void pack_offsets_body(
                 pack_decode::place(
                     reinterpret_cast<const pack_decode::item *>(items) + i, reinterpret_cast<pack_decode::item *>(packed) + i, off,
                     pack_length<BATCH>(lengths, decode, i, batch), reserved, capacity);
-            } else if (decode == 0) {
+            } else if (decode == 0 || INDEXED) {
                 pack_encode::place(
                     reinterpret_cast<const pack_encode::item *>(items) + i, reinterpret_cast<pack_encode::item *>(packed) + i, off, 0,
                     reserved, capacity);
@@ -343,6 +361,10 @@ struct pack_scan {
     const void *lengths;
     u64 *tile_sums, *offsets, *summary;
     pack_batch batch;
+    /* kPackIndexed alone (0 and NULL for every other kind): what kind 0 is given as arguments of pack_offsets_kernel -- the
+     * items are `lengths` */
+    u64 align_mask, out_capacity;
+    void *packed;
 };
 
 /* The records of a packed decode launch that are not the scan's to write, a thread each (ONE kernel for both uses):
@@ -354,14 +376,24 @@ __global__ __launch_bounds__(kPackThreads) void unpack_records_kernel(
     const hufd_dec_item *items, hufd_dec_item *packed, const hufd_chunk_rec *chunk_rec, hufd_chunk_rec *packed_rec, u32 n,
     pack_scan scan) {
     if (scan.pass == 1) {
-        pack_tile_sums_body<true>(
-            scan.lengths, scan.decode, scan.n_items, scan.tile_items, 0, scan.tile_sums, scan.batch);
+        if (scan.decode == kPackIndexed) {
+            pack_tile_sums_body<true, true>(
+                scan.lengths, kPackIndexed, scan.n_items, scan.tile_items, scan.align_mask, scan.tile_sums, scan.batch);
+        } else {
+            pack_tile_sums_body<true>(scan.lengths, scan.decode, scan.n_items, scan.tile_items, 0, scan.tile_sums, scan.batch);
+        }
         return;
     }
     if (scan.pass == 2) {
-        pack_offsets_body<true>(
-            nullptr, scan.lengths, scan.decode, scan.n_items, scan.tile_items, 0, 0, scan.tile_sums, scan.offsets, nullptr,
-            scan.summary, scan.batch);
+        if (scan.decode == kPackIndexed) {
+            pack_offsets_body<true, true>(
+                scan.lengths, scan.lengths, kPackIndexed, scan.n_items, scan.tile_items, scan.align_mask, scan.out_capacity,
+                scan.tile_sums, scan.offsets, scan.packed, scan.summary, scan.batch);
+        } else {
+            pack_offsets_body<true>(
+                nullptr, scan.lengths, scan.decode, scan.n_items, scan.tile_items, 0, 0, scan.tile_sums, scan.offsets, nullptr,
+                scan.summary, scan.batch);
+        }
         return;
     }
     const u32 k = blockIdx.x * kPackThreads + threadIdx.x;
@@ -403,10 +435,11 @@ int pack_offsets_launch(
     return (int)hipGetLastError();
 }
 
-/* the same two passes with the batch kinds: the bodies unpack_records_kernel hosts */
+/* the same two passes with the batch kinds: the bodies unpack_records_kernel hosts (align, out_capacity, packed: kPackIndexed's) */
 int pack_batch_launch(
     const void *lengths, uint32_t decode, uint32_t n_items, uint32_t tile_items, uint64_t *tile_sums, uint64_t *offsets,
-    uint64_t *summary, const pack_batch &batch, hipStream_t st) {
+    uint64_t *summary, const pack_batch &batch, hipStream_t st, uint64_t align = 1, uint64_t out_capacity = 0,
+    void *packed = nullptr) {
     /* (a directory of no items is still a record, a total and a status: one workgroup) */
     const uint32_t tiles = n_items ? hufk_pack_tiles(n_items, tile_items) : 1u;
     pack_scan scan{};
@@ -418,6 +451,9 @@ int pack_batch_launch(
     scan.offsets = offsets;
     scan.summary = summary;
     scan.batch = batch;
+    scan.align_mask = align - 1;
+    scan.out_capacity = out_capacity;
+    scan.packed = packed;
     for (scan.pass = tiles > 1 ? 1 : 2; scan.pass <= 2; ++scan.pass) { /* (nobody reads the last tile's sums) */
         hipLaunchKernelGGL(
             unpack_records_kernel, dim3(scan.pass == 1 ? tiles - 1 : tiles), dim3(kPackThreads), kPackLdsBytes, st,
@@ -486,6 +522,22 @@ int hufk_batch_index_scan(
     batch.count = device_blocks;
     return pack_batch_launch(
         index, kPackIndex, most_blocks, tile_blocks, tile_sums, index, reinterpret_cast<uint64_t *>(status), batch, (hipStream_t)stream);
+}
+
+int hufk_pack_offsets_indexed(
+    const struct hufd_enc_item *items, uint32_t n_items, uint32_t tile_items, uint64_t align, uint64_t capacity,
+    const uint64_t *directory, const uint64_t *index, uint64_t index_capacity, uint64_t *tile_sums, uint64_t *offsets,
+    struct hufd_enc_item *packed, uint64_t *summary, void *stream) {
+    if (n_items == 0 || tile_items == 0) {
+        return 0;
+    }
+    pack_batch batch{};
+    batch.capacity = index_capacity;
+    batch.index = const_cast<uint64_t *>(index); /* (read only by this kind) */
+    batch.count = directory + 2 * (uint64_t)n_items;
+    batch.directory = directory;
+    return pack_batch_launch(
+        items, kPackIndexed, n_items, tile_items, tile_sums, offsets, summary, batch, (hipStream_t)stream, align, capacity, packed);
 }
 
 int hufk_unpack_blank(const struct hufd_dec_item *items, uint32_t n_items, struct hufd_dec_item *packed, void *stream) {

@@ -8,6 +8,7 @@
 #include "engine.h"
 
 #include <aws/compression/huffman_amd_batch_index.h>
+#include <aws/compression/huffman_amd_packed_index.h>
 #include <aws/compression/huffman_amd_build.h>
 #include <aws/compression/huffman_amd_fit.h>
 #include <aws/compression/huffman_amd_index.h>
@@ -1315,6 +1316,44 @@ static int enc_plan_reserve_packed(struct aws_huffman_amd_encode_plan *p, size_t
     return 0;
 }
 
+/* what a packed launch asks of its own arguments (the plan is not looked into) */
+static bool packed_launch_args_ok(
+    const struct aws_huffman_amd_encode_plan *p, const void *device_output, uint64_t output_capacity, const uint64_t *device_offsets,
+    uint32_t align) {
+    return p && device_offsets && !((uintptr_t)device_offsets & 7u) && align != 0 && align <= 4096 && !(align & (align - 1)) &&
+           (device_output || !output_capacity);
+}
+
+/* a packed launch of a plan without items: offsets[0] = 0, and a size of nothing */
+static int enc_plan_launch_packed_empty(struct aws_huffman_amd_encode_plan *p, uint64_t *device_offsets, void *st) {
+    ON_DEVICE(p->engine->device);
+    const int e = hufs_memset(device_offsets, 0, sizeof(uint64_t), st);
+    if (e) {
+        return raise_hip(e);
+    }
+    p->packed = false;
+    p->packed_sized = true;
+    return AWS_OP_SUCCESS;
+}
+
+/* the scan's tile for the plan's items, with the second record array and the scan's scratch reserved for them */
+static int enc_plan_packed_tile_items(struct aws_huffman_amd_encode_plan *p, uint32_t *tile_items) {
+    *tile_items = hufk_pack_tile_items(p->n_items, __atomic_load_n(&s_pack_tile_items, __ATOMIC_RELAXED));
+    ON_DEVICE(p->engine->device);
+    const int e = enc_plan_reserve_packed(p, p->n_items, hufk_pack_tiles(p->n_items, *tile_items));
+    return e ? raise_hip(e) : AWS_OP_SUCCESS;
+}
+
+/* the encode pass of a packed launch, over the second record array the scan has made */
+static int enc_plan_launch_packed_items(struct aws_huffman_amd_encode_plan *p, const void *device_input, void *device_output, void *stream) {
+    if (enc_plan_launch_items(p, p->d_packed_items, device_input, device_output, false, stream, NULL)) {
+        return AWS_OP_ERR;
+    }
+    p->packed = true;
+    p->packed_sized = true;
+    return AWS_OP_SUCCESS;
+}
+
 int aws_huffman_amd_encode_plan_launch_packed(
     struct aws_huffman_amd_encode_plan *p,
     const void *device_input,
@@ -1324,8 +1363,7 @@ int aws_huffman_amd_encode_plan_launch_packed(
     uint32_t align,
     void *stream) {
 
-    if (!p || !device_offsets || ((uintptr_t)device_offsets & 7u) || align == 0 || align > 4096 || (align & (align - 1)) ||
-        (!device_output && output_capacity)) {
+    if (!packed_launch_args_ok(p, device_output, output_capacity, device_offsets, align)) {
         return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
     }
     if (engine_never_fitted(p->engine)) {
@@ -1333,22 +1371,11 @@ int aws_huffman_amd_encode_plan_launch_packed(
     }
     void *st = stream ? stream : p->engine->stream;
     if (p->n_items == 0) {
-        ON_DEVICE(p->engine->device);
-        const int e = hufs_memset(device_offsets, 0, sizeof(uint64_t), st);
-        if (e) {
-            return raise_hip(e);
-        }
-        p->packed = false;
-        p->packed_sized = true;
-        return AWS_OP_SUCCESS;
+        return enc_plan_launch_packed_empty(p, device_offsets, st);
     }
-    const uint32_t tile_items = hufk_pack_tile_items(p->n_items, __atomic_load_n(&s_pack_tile_items, __ATOMIC_RELAXED));
-    {
-        ON_DEVICE(p->engine->device);
-        const int e = enc_plan_reserve_packed(p, p->n_items, hufk_pack_tiles(p->n_items, tile_items));
-        if (e) {
-            return raise_hip(e);
-        }
+    uint32_t tile_items = 0;
+    if (enc_plan_packed_tile_items(p, &tile_items)) {
+        return AWS_OP_ERR;
     }
     /* the lengths (into the plan's result records), the offsets and the second record array from them, the encode pass over
      * that array (its records replace the lengths): three stages on one stream */
@@ -1364,12 +1391,7 @@ int aws_huffman_amd_encode_plan_launch_packed(
             return raise_hip(e);
         }
     }
-    if (enc_plan_launch_items(p, p->d_packed_items, device_input, device_output, false, stream, NULL)) {
-        return AWS_OP_ERR;
-    }
-    p->packed = true;
-    p->packed_sized = true;
-    return AWS_OP_SUCCESS;
+    return enc_plan_launch_packed_items(p, device_input, device_output, stream);
 }
 
 int aws_huffman_amd_encode_plan_packed_size(
@@ -2759,7 +2781,18 @@ static int enc_plan_reserve_block_index(struct aws_huffman_amd_encode_plan *p, s
     return 0;
 }
 
-int aws_huffman_amd_encode_plan_block_index(
+/* what a batch index asks of its arguments */
+static bool block_index_args_ok(
+    const struct aws_huffman_amd_encode_plan *p, const void *device_input, uint64_t block_symbols,
+    const struct aws_huffman_amd_item_blocks *device_directory, const uint64_t *device_index, uint64_t index_capacity,
+    const uint32_t *device_status) {
+    return p && device_directory && !((uintptr_t)device_directory & 7u) && !((uintptr_t)device_index & 7u) &&
+           !((uintptr_t)device_status & 3u) && (device_index == NULL) == (index_capacity == 0) && index_block_symbols_ok(block_symbols) &&
+           (!p->n_items || device_input);
+}
+
+/* the directory, the hot pass and the scan of a plan's batch index on `stream`: the arguments are good, the engine fitted */
+static int enc_plan_block_index_enqueue(
     struct aws_huffman_amd_encode_plan *p,
     const void *device_input,
     uint64_t block_symbols,
@@ -2769,18 +2802,7 @@ int aws_huffman_amd_encode_plan_block_index(
     uint32_t *device_status,
     void *stream) {
 
-    if (hufs_device_count() <= 0) {
-        return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION); /* no GPU: there is no CPU path */
-    }
-    if (!p || !device_directory || ((uintptr_t)device_directory & 7u) || ((uintptr_t)device_index & 7u) ||
-        ((uintptr_t)device_status & 3u) || (device_index == NULL) != (index_capacity == 0) || !index_block_symbols_ok(block_symbols) ||
-        (p->n_items && !device_input)) {
-        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
-    }
     struct aws_huffman_amd_engine *eng = p->engine;
-    if (engine_never_fitted(eng)) {
-        return aws_raise_error(AWS_ERROR_INVALID_STATE);
-    }
     ON_DEVICE(eng->device);
     pthread_mutex_lock(&eng->spare_lock);
     if (!eng->d_index_tile_sums) { /* (as aws_huffman_amd_block_index: the engine's first call of either) */
@@ -2815,15 +2837,96 @@ int aws_huffman_amd_encode_plan_block_index(
     job.item_tile_sums = p->d_block_index_tile_sums;
     job.summary = p->d_block_index_summary;
     job.index_tile_sums = index_tile_sums;
-    int err = hufk_batch_block_index(&job, stream ? stream : eng->stream);
-    if (!err) { /* (the plan's records and scratch are read on this stream: whoever gets its arrays next waits, as for a launch) */
-        err = plan_mark_done(&p->done_event, &p->done_on_engine_stream, eng, stream);
-    }
+    const int err = hufk_batch_block_index(&job, stream ? stream : eng->stream);
     if (err) {
         return raise_hip(err);
     }
     p->block_indexed = true;
     return AWS_OP_SUCCESS;
+}
+
+int aws_huffman_amd_encode_plan_block_index(
+    struct aws_huffman_amd_encode_plan *p,
+    const void *device_input,
+    uint64_t block_symbols,
+    struct aws_huffman_amd_item_blocks *device_directory,
+    uint64_t *device_index,
+    uint64_t index_capacity,
+    uint32_t *device_status,
+    void *stream) {
+
+    if (hufs_device_count() <= 0) {
+        return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION); /* no GPU: there is no CPU path */
+    }
+    if (!block_index_args_ok(p, device_input, block_symbols, device_directory, device_index, index_capacity, device_status)) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    if (engine_never_fitted(p->engine)) {
+        return aws_raise_error(AWS_ERROR_INVALID_STATE);
+    }
+    if (enc_plan_block_index_enqueue(p, device_input, block_symbols, device_directory, device_index, index_capacity, device_status, stream)) {
+        return AWS_OP_ERR;
+    }
+    /* (the plan's records and scratch are read on this stream: whoever gets its arrays next waits, as for a launch) */
+    ON_DEVICE(p->engine->device);
+    const int err = plan_mark_done(&p->done_event, &p->done_on_engine_stream, p->engine, stream);
+    return err ? raise_hip(err) : AWS_OP_SUCCESS;
+}
+
+/* ------------------------------------------------------------------ a packed launch that makes the index (huffman_amd_packed_index.h) */
+
+int aws_huffman_amd_encode_plan_launch_packed_indexed(
+    struct aws_huffman_amd_encode_plan *p,
+    const void *device_input,
+    void *device_output,
+    uint64_t output_capacity,
+    uint64_t *device_offsets,
+    uint32_t align,
+    uint64_t block_symbols,
+    struct aws_huffman_amd_item_blocks *device_directory,
+    uint64_t *device_index,
+    uint64_t index_capacity,
+    uint32_t *device_status,
+    void *stream) {
+
+    if (hufs_device_count() <= 0) {
+        return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION); /* no GPU: there is no CPU path */
+    }
+    if (!packed_launch_args_ok(p, device_output, output_capacity, device_offsets, align) || !device_index ||
+        !block_index_args_ok(p, device_input, block_symbols, device_directory, device_index, index_capacity, device_status)) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    if (engine_never_fitted(p->engine)) {
+        return aws_raise_error(AWS_ERROR_INVALID_STATE);
+    }
+    uint32_t tile_items = 0;
+    if (p->n_items && enc_plan_packed_tile_items(p, &tile_items)) {
+        return AWS_OP_ERR;
+    }
+    /* the index (its hot pass is the launch's length pass), the offsets and the second record array from it, the encode pass
+     * over that array: three stages on one stream, the symbols read twice */
+    if (enc_plan_block_index_enqueue(p, device_input, block_symbols, device_directory, device_index, index_capacity, device_status, stream)) {
+        return AWS_OP_ERR;
+    }
+    void *st = stream ? stream : p->engine->stream;
+    if (p->n_items == 0) {
+        if (enc_plan_launch_packed_empty(p, device_offsets, st)) {
+            return AWS_OP_ERR;
+        }
+        ON_DEVICE(p->engine->device);
+        const int err = plan_mark_done(&p->done_event, &p->done_on_engine_stream, p->engine, stream);
+        return err ? raise_hip(err) : AWS_OP_SUCCESS;
+    }
+    {
+        ON_DEVICE(p->engine->device);
+        const int e = hufk_pack_offsets_indexed(
+            p->d_items, p->n_items, tile_items, align, output_capacity, (const uint64_t *)device_directory, device_index, index_capacity,
+            p->d_pack_tile_sums, device_offsets, p->d_packed_items, p->d_pack_summary, st);
+        if (e) {
+            return raise_hip(e);
+        }
+    }
+    return enc_plan_launch_packed_items(p, device_input, device_output, stream);
 }
 
 int aws_huffman_amd_encode_plan_block_index_size(struct aws_huffman_amd_encode_plan *p, uint64_t *entries, void *stream) {

@@ -28,7 +28,9 @@
  * and any symbols of any items with aws_huffman_amd_decode_plan_reset_item_symbol_ranges, as huffman_amd_ranges.h does for
  * one stream; aws_huffman_amd_locate_item_symbols says where a symbol of an item starts.
  *
- * Out of this interface: an index made by the encode launch itself, and aws_huffman_amd_shards_*.
+ * Out of this interface: an index made by a PLAIN encode launch (a packed launch makes it in place of its length pass:
+ * aws_huffman_amd_encode_plan_launch_packed_indexed, huffman_amd_packed_index.h, one call for the last two lines above with
+ * one read of the symbols fewer), and aws_huffman_amd_shards_*.
  */
 
 #include <aws/compression/huffman_amd_ranges.h>
