@@ -377,10 +377,7 @@ __device__ __forceinline__ void dec_emit_fast_chunk(
     u8 *d_out,
     const u16 *cp_tab,
     const u16 *lane_count,
-    const u8 *chunk_regular,
-    const u32 *chunk_fn,
-    const u32 *chunk_entry,
-    const u64 *chunk_base,
+    const hufd_emit_rec *emit_rec,
     hufd_dec_result *results,
     u32 *slow_list, /* chunks left to dec_emit_kernel */
     u32 *slow_count,
@@ -389,7 +386,6 @@ __device__ __forceinline__ void dec_emit_fast_chunk(
     u32 stage_limit /* symbols the stage of this launch holds (HUFD_DEC_STAGE_BYTES, or less: emit_lds_bytes) */) {
 
     emit_shared<LB> &sh = *reinterpret_cast<emit_shared<LB> *>(dyn_lds);
-    const u32 ns = tb.n_states;
     const u32 t = threadIdx.x;
     /* my quarter of two sub-chunks.  In a chunk that holds the end of a stream only the first lanes have data: there a
      * thread takes two NEIGHBOURING sub-chunks and the threads are numbered sub-chunks first, so that the idle ones fill
@@ -409,29 +405,30 @@ __device__ __forceinline__ void dec_emit_fast_chunk(
         const u32 i = t + j * lut_stride;
         lut_raw[j] = i < (1u << LB) ? tb.dec_lut[i >> (LB - tb.lut_bits)] : 0u;
     }
-    const u32 centry = chunk_entry[c];
-    if (!(centry & 0x100u)) {
+    /* what the scan stage left of the chunk for the state it is truly entered in (hufd_emit_rec), beside the plan's record:
+     * two loads that depend on nothing, and nothing is loaded behind them before the decision */
+    const hufd_emit_rec erec = emit_rec[c];
+    const hufd_chunk_rec rec = chunk_rec[c]; /* (not chunk -> item -> its record) */
+    if (!(erec.flags & HUFD_EMIT_REACHED)) {
         return; /* the stream ended before this chunk */
     }
-    const u32 s0 = centry & 0xFFu;
-    const hufd_chunk_rec rec = chunk_rec[c]; /* (asked for with the chunk's entry: not chunk -> item -> its record) */
+    const u32 s0 = erec.flags & HUFD_EMIT_STATE_MASK;
     const u64 valid = rec.valid;
     /* lanes whose sub-chunk and the 8 bytes after it lie inside the stream (dec_sync_one: the others are idle or "careful") */
     if (!TAIL && valid < (u64)HUFD_DEC_CHUNK_BYTES + 8u) {
         return; /* the other instantiation's */
     }
     const u32 n_full = !TAIL ? HUFD_DEC_LANES : (valid >= 8u ? (u32)((valid - 8u) / HUFD_DEC_SUB_BYTES) : 0u);
-    const u64 cbase = chunk_base[c];
+    const u64 cbase = erec.base;
     const u16 *cpt = cp_tab + (u64)c * kCpRows * HUFD_DEC_LANES;
     const u32 merged_row = (kQuarters - 1) * HUFD_DEC_LANES;
-    const u32 f0 = chunk_fn[(u64)c * ns + s0];
-    const u32 chunk_symbols = wide_count(f0);
+    const u32 chunk_symbols = erec.symbols;
     /* all the same for the whole workgroup */
-    const u32 regular = chunk_regular[c]; /* 1: all lanes whole; 2: the chunk that holds the end of the stream */
+    const u32 regular = (erec.flags & HUFD_EMIT_REGULAR_MASK) >> HUFD_EMIT_REGULAR_SHIFT; /* 1: all lanes whole; 2: the chunk that holds the end of the stream */
     if (TAIL && regular == 3) {
         return; /* fewer than 136 bytes: dec_emit_tail does the whole chunk */
     }
-    const bool fits = regular != 0 && (regular == 2 || !wide_stop(f0)) && ((cpt[merged_row] >> s0) & 1u) != 0 &&
+    const bool fits = regular != 0 && (regular == 2 || !(erec.flags & HUFD_EMIT_STOPS)) && (erec.flags & HUFD_EMIT_MERGED) != 0 &&
                       cbase + chunk_symbols <= rec.out_cap;
     const bool fast = fits && chunk_symbols + 16 <= stage_limit &&
                       (lds_offset_of(sh.wlut) & ((4u << LB) - 1u)) == 0 && SURE <= row_walk(LB, tb.max_bits).sure;
@@ -675,10 +672,7 @@ __global__ __launch_bounds__(kEmitFastThreads, TAIL ? 6 : 8) void dec_emit_fast_
     u8 *d_out,
     const u16 *cp_tab,
     const u16 *lane_count,
-    const u8 *chunk_regular,
-    const u32 *chunk_fn,
-    const u32 *chunk_entry,
-    const u64 *chunk_base,
+    const hufd_emit_rec *emit_rec,
     hufd_dec_result *results,
     u32 *slow_list, /* chunks left to dec_emit_kernel */
     u32 *slow_count,
@@ -686,8 +680,8 @@ __global__ __launch_bounds__(kEmitFastThreads, TAIL ? 6 : 8) void dec_emit_fast_
     u32 *dense_count,
     u32 stage_limit /* symbols the stage of this launch holds (HUFD_DEC_STAGE_BYTES, or less: emit_lds_bytes) */) {
     dec_emit_fast_chunk<LB, TAIL, SURE>(
-        TAIL ? tail_chunks[blockIdx.x] : blockIdx.x, tb, chunk_rec, d_in, d_out, cp_tab, lane_count, chunk_regular, chunk_fn,
-        chunk_entry, chunk_base, results, slow_list, slow_count, dense_list, dense_count, stage_limit);
+        TAIL ? tail_chunks[blockIdx.x] : blockIdx.x, tb, chunk_rec, d_in, d_out, cp_tab, lane_count, emit_rec, results, slow_list,
+        slow_count, dense_list, dense_count, stage_limit);
 }
 
 /*
@@ -706,10 +700,7 @@ __global__ __launch_bounds__(kEmitFastThreads, 4) void dec_emit_big_kernel(
     u8 *d_out,
     const u16 *cp_tab,
     const u16 *lane_count,
-    const u8 *chunk_regular,
-    const u32 *chunk_fn,
-    const u32 *chunk_entry,
-    const u64 *chunk_base,
+    const hufd_emit_rec *emit_rec,
     hufd_dec_result *results,
     u32 *slow_list,
     u32 *slow_count,
@@ -722,8 +713,8 @@ __global__ __launch_bounds__(kEmitFastThreads, 4) void dec_emit_big_kernel(
         }
         /* (a chunk that does not go through here after all is left to the long way, not listed for this kernel again) */
         dec_emit_fast_chunk<LB, false, SURE>(
-            big_list[k], tb, chunk_rec, d_in, d_out, cp_tab, lane_count, chunk_regular, chunk_fn, chunk_entry, chunk_base, results,
-            slow_list, slow_count, slow_list, slow_count, kEmitBigStage);
+            big_list[k], tb, chunk_rec, d_in, d_out, cp_tab, lane_count, emit_rec, results, slow_list, slow_count, slow_list,
+            slow_count, kEmitBigStage);
         __syncthreads(); /* the table and the stage are written again */
     }
 }
@@ -1126,8 +1117,7 @@ hipLaunchKernelGGL(                                                             
     (dec_emit_fast_kernel<LBV, TAILV, SUREV>), dim3(GRID), dim3((TAILV) && (LBV) == 10 ? tail_block : kEmitFastThreads), \
     emit_lds_bytes<LBV>(TAILV ? tail_stage : HUFD_DEC_STAGE_BYTES), STREAMV, a->tables, a->chunk_rec,              \
     emit_single_chunks, (const u8 *)a->d_in, (u8 *)a->d_out, (const u16 *)a->cp_tab, (const u16 *)a->lane_count,   \
-    (const u8 *)a->chunk_regular, (const u32 *)a->chunk_fn, (const u32 *)a->chunk_entry,                           \
-    (const u64 *)a->chunk_base, a->results, a->emit_list, emit_count,                                            \
+    (const hufd_emit_rec *)a->emit_rec, a->results, a->emit_list, emit_count,                                      \
     !TAILV && big ? a->dense_list : a->emit_list, !TAILV && big ? dense_count : emit_count,                  \
     TAILV ? tail_stage : HUFD_DEC_STAGE_BYTES)
     /* dec_emit_fast<TAIL>'s workgroup: four quarters to two sub-chunks a thread over the most whole lanes a wide chunk of the
@@ -1232,8 +1222,8 @@ do {                                                                            
         (dec_emit_big_kernel<LBV, SUREV>),                                                                         \
         dim3(persistent_grid(dec_emit_big_kernel<LBV, SUREV>, kEmitFastThreads, lds, a->n_chunks)),                 \
         dim3(kEmitFastThreads), lds, st, a->tables, a->chunk_rec, (const u8 *)a->d_in, (u8 *)a->d_out,             \
-        (const u16 *)a->cp_tab, (const u16 *)a->lane_count, (const u8 *)a->chunk_regular, (const u32 *)a->chunk_fn, \
-        (const u32 *)a->chunk_entry, (const u64 *)a->chunk_base, a->results, a->emit_list, emit_count,          \
+        (const u16 *)a->cp_tab, (const u16 *)a->lane_count, (const hufd_emit_rec *)a->emit_rec, a->results,        \
+        a->emit_list, emit_count,                                                                               \
         (const u32 *)a->dense_list, (const u32 *)dense_count);                                                  \
 } while (0)
     if (!big) {

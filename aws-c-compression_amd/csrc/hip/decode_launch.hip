@@ -29,13 +29,35 @@ __device__ void dec_finish_item(
     }
 }
 
+/* The emit record of chunk c (device_types.h), entered in `state` with `total` symbols of its item in front of it; f: the
+ * chunk's function of that state (not looked at for a chunk the stream does not reach).  The sync stage has run: what it
+ * found of the chunk is in chunk_regular and in the last checkpoint row. */
+__device__ __forceinline__ hufd_emit_rec emit_rec_of(
+    u32 c, u32 state, bool stopped, u64 total, u32 f, const u8 *chunk_regular, const u16 *cp_tab) {
+    hufd_emit_rec r;
+    r.flags = state & HUFD_EMIT_STATE_MASK;
+    r.symbols = 0;
+    r.base = total;
+    if (!stopped) {
+        const u32 regular = chunk_regular[c];
+        const u32 merged = cp_tab[((u64)c * kCpRows + (kQuarters - 1)) * HUFD_DEC_LANES];
+        r.flags |= HUFD_EMIT_REACHED | (regular << HUFD_EMIT_REGULAR_SHIFT) | (((merged >> state) & 1u) ? HUFD_EMIT_MERGED : 0u) |
+                   (wide_stop(f) ? HUFD_EMIT_STOPS : 0u);
+        r.symbols = wide_count(f);
+    }
+    return r;
+}
+
 __global__ __launch_bounds__(256) void dec_scan_small_kernel(
     const hufd_dec_item *items,
     u32 n_items,
     u32 ns,
     const u32 *chunk_fn,
+    const u8 *chunk_regular,
+    const u16 *cp_tab,
     u32 *chunk_entry,
     u64 *chunk_base,
+    hufd_emit_rec *emit_rec,
     hufd_dec_item_state *states,
     hufd_dec_result *results) {
 
@@ -57,8 +79,9 @@ __global__ __launch_bounds__(256) void dec_scan_small_kernel(
         const u32 c = it.first_chunk + k;
         chunk_entry[c] = entry_pack(state, !stopped);
         chunk_base[c] = total;
+        const u32 f = stopped ? 0u : chunk_fn[(u64)c * ns + state];
+        emit_rec[c] = emit_rec_of(c, state, stopped, total, f, chunk_regular, cp_tab);
         if (!stopped) {
-            const u32 f = chunk_fn[(u64)c * ns + state];
             total += wide_count(f);
             stopped = wide_stop(f);
             state = wide_state(f);
@@ -185,8 +208,11 @@ __global__ __launch_bounds__(256) void dec_scan_apply_kernel(
     u32 ns,
     const u32 *chunk_fn,
     const u32 *run_fn,
+    const u8 *chunk_regular,
+    const u16 *cp_tab,
     u32 *chunk_entry,
     u64 *chunk_base,
+    hufd_emit_rec *emit_rec,
     hufd_dec_item_state *states,
     hufd_dec_result *results) {
     u32 *fn = reinterpret_cast<u32 *>(dyn_lds);
@@ -238,6 +264,16 @@ __global__ __launch_bounds__(256) void dec_scan_apply_kernel(
                 state = wide_state(f);
             }
         }
+    }
+    /* the emit records, a thread a chunk: what the sixteen threads above have just written, the chunk's function of that
+     * state (still in LDS) and what the sync stage found -- loads that the chains above do not wait for */
+    __syncthreads();
+    for (u32 q = threadIdx.x; q < n; q += blockDim.x) {
+        const u32 c = it.first_chunk + k * kRunChunks + q;
+        const u32 centry = chunk_entry[c];
+        const u32 state = centry & 0xFFu;
+        const bool stopped = !(centry & 0x100u);
+        emit_rec[c] = emit_rec_of(c, state, stopped, chunk_base[c], stopped ? 0u : fn[q * ns + state], chunk_regular, cp_tab);
     }
 }
 
@@ -522,7 +558,7 @@ static int decode_launch_stages(const struct hufk_decode_args *a, const struct h
     if (a->n_tiny != a->n_items && a->n_large != a->n_items) { /* (as in the encoder: nothing to scan, and no empty item's record to write, in a plan of thread-per-item items only; nor in one of long items only -- one stream --, which are dec_scan_runs / _top / _apply's) */
         hipLaunchKernelGGL(
             dec_scan_small_kernel, dim3((a->n_items + 255) / 256), dim3(256), 0, st, a->items, a->n_items, ns, a->chunk_fn,
-            a->chunk_entry, a->chunk_base, a->states, a->results);
+            (const u8 *)a->chunk_regular, (const u16 *)a->cp_tab, a->chunk_entry, a->chunk_base, a->emit_rec, a->states, a->results);
     }
     hufk_host::decode_items_stage(items_pass, st);
     if (a->n_large) {
@@ -531,7 +567,8 @@ static int decode_launch_stages(const struct hufk_decode_args *a, const struct h
             dec_scan_runs_kernel, dim3(a->n_runs), dim3(256), lds, st, a->items, a->runs, ns, a->chunk_fn, a->run_fn);
         hipLaunchKernelGGL(
             dec_scan_apply_kernel, dim3(a->n_runs), dim3(256), scan_apply_lds_bytes(ns), st, a->items, a->runs, ns, a->chunk_fn,
-            (const u32 *)a->run_fn, a->chunk_entry, a->chunk_base, a->states, a->results);
+            (const u32 *)a->run_fn, (const u8 *)a->chunk_regular, (const u16 *)a->cp_tab, a->chunk_entry, a->chunk_base,
+            a->emit_rec, a->states, a->results);
     }
     hufk_host::decode_sync_true_stage(a, st, state);
     stage_mark(a->stage_events, 2, st);

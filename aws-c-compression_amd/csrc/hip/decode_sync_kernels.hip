@@ -1221,6 +1221,7 @@ __global__ __launch_bounds__(HUFD_DEC_LANES, 8) void dec_sync_true_kernel(
     u16 *lane_count,
     u8 *chunk_regular,
     const u32 *chunk_entry,
+    hufd_emit_rec *emit_rec, /* the scan stage's, made while the chunk was still marked kRegularFew: what is decided here goes in */
     const u32 *list, /* dec_sync_few's chunks */
     const u32 *list_count) {
 
@@ -1245,6 +1246,7 @@ __global__ __launch_bounds__(HUFD_DEC_LANES, 8) void dec_sync_true_kernel(
             /* the stream ended before this chunk: nobody emits it, and it must not look regular to anybody */
             if (lane == 0) {
                 chunk_regular[c] = 0;
+                emit_rec[c].flags &= ~(HUFD_EMIT_REGULAR_MASK | HUFD_EMIT_MERGED);
             }
             continue;
         }
@@ -1302,6 +1304,9 @@ __global__ __launch_bounds__(HUFD_DEC_LANES, 8) void dec_sync_true_kernel(
         }
         if (lane == 0) {
             chunk_regular[c] = good ? 1 : 0;
+            /* (sub-chunk 0 is entered in the chunk's own entry state: its merged-state mask, written above, is that one bit) */
+            emit_rec[c].flags = (emit_rec[c].flags & ~(HUFD_EMIT_REGULAR_MASK | HUFD_EMIT_MERGED)) |
+                                (good ? (1u << HUFD_EMIT_REGULAR_SHIFT) | HUFD_EMIT_MERGED : 0u);
             sh.bad = 0;
         }
         __syncthreads();
@@ -1561,13 +1566,13 @@ void hufk_host::decode_sync_true_stage(const struct hufk_decode_args *a, hipStre
             dim3(persistent_grid(dec_sync_true_kernel<10>, HUFD_DEC_LANES, (uint32_t)sizeof(few_shared<10>), a->n_chunks)),
             dim3(HUFD_DEC_LANES), (uint32_t)sizeof(few_shared<10>), st, a->tables, a->chunk_rec, (const u8 *)a->d_in,
             (const u16 *)a->fn_tab, a->cp_tab, a->lane_count, a->chunk_regular, (const u32 *)a->chunk_entry,
-            (const u32 *)a->slow_list, (const u32 *)(a->counters + HUFK_DEC_COUNT_FEW));
+            a->emit_rec, (const u32 *)a->slow_list, (const u32 *)(a->counters + HUFK_DEC_COUNT_FEW));
     } else {
         hipLaunchKernelGGL(
             (dec_sync_true_kernel<12>),
             dim3(persistent_grid(dec_sync_true_kernel<12>, HUFD_DEC_LANES, (uint32_t)sizeof(few_shared<12>), a->n_chunks)),
             dim3(HUFD_DEC_LANES), (uint32_t)sizeof(few_shared<12>), st, a->tables, a->chunk_rec, (const u8 *)a->d_in,
             (const u16 *)a->fn_tab, a->cp_tab, a->lane_count, a->chunk_regular, (const u32 *)a->chunk_entry,
-            (const u32 *)a->slow_list, (const u32 *)(a->counters + HUFK_DEC_COUNT_FEW));
+            a->emit_rec, (const u32 *)a->slow_list, (const u32 *)(a->counters + HUFK_DEC_COUNT_FEW));
     }
 }

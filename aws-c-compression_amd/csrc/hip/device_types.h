@@ -220,6 +220,22 @@ struct hufd_chunk_rec {
     uint32_t reserved;
 };
 
+/* one per chunk, written by the scan stage of every launch (dec_scan_small, dec_scan_apply) for the state the chunk is truly
+ * entered in: everything dec_emit_fast decides on before it asks for the chunk's bytes, in ONE load beside hufd_chunk_rec
+ * (it used to be chunk_entry[c], then chunk_fn[c][s0] behind it, with chunk_base, chunk_regular and a checkpoint word
+ * beside them).  dec_sync_true, which runs behind the scan, rewrites the two fields it decides for its chunks. */
+#define HUFD_EMIT_STATE_MASK 0xFFu      /* flags: s0, the state the chunk is entered in ... */
+#define HUFD_EMIT_REACHED 0x100u        /* ... the stream reaches this chunk (the two as in chunk_entry) */
+#define HUFD_EMIT_REGULAR_SHIFT 9u      /* chunk_regular[c], three bits */
+#define HUFD_EMIT_REGULAR_MASK (7u << HUFD_EMIT_REGULAR_SHIFT)
+#define HUFD_EMIT_MERGED 0x1000u        /* bit s0 of sub-chunk 0's merged-state mask (the last checkpoint row, lane 0) */
+#define HUFD_EMIT_STOPS 0x2000u         /* the true path stops inside this chunk (wide_stop of chunk_fn[c][s0]) */
+struct hufd_emit_rec {
+    uint32_t flags;
+    uint32_t symbols; /* wide_count of chunk_fn[c][s0]: the symbols of the true path that start in this chunk */
+    uint64_t base;    /* chunk_base[c]: the symbols of the item in front of this chunk */
+};
+
 /* Where the items of a plan that is made on the device come from (plan_kernels.hip): the caller's records in DEVICE memory,
  * a stride, what an encode launch left, a packed buffer's offsets or ranges of an indexed stream's blocks (decode) */
 #define HUFD_ITEMS_DEVICE_ARRAY 0u

@@ -117,6 +117,7 @@ struct hufk_decode_args {
     uint32_t *tail_entry;   /* [n_chunks] scratch: state in which the last whole lane of an end-of-stream chunk leaves */
     uint32_t *chunk_entry; /* [n_chunks] scratch */
     uint64_t *chunk_base;  /* [n_chunks] scratch */
+    struct hufd_emit_rec *emit_rec; /* [n_chunks] scratch: the scan stage's record of every chunk for dec_emit_fast */
     const struct hufd_chunk_rec *chunk_rec; /* [n_chunks] built with the plan */
     void *side_stream;  /* NULL, or a stream of the engine's for the kernels of the chunks streams end in ... */
     void *fork_event;   /* ... and two events to fork it off the launch's stream and join it again */

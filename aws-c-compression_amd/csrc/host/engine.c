@@ -1544,6 +1544,7 @@ int aws_huffman_amd_encode_plan_results(
     X(d_tail_entry, (cc) * sizeof(uint32_t))                                                                           \
     X(d_chunk_entry, (cc) * sizeof(uint32_t))                                                                          \
     X(d_chunk_base, (cc) * sizeof(uint64_t))                                                                           \
+    X(d_emit_rec, (cc) * sizeof(struct hufd_emit_rec))                                                                 \
     X(d_chunk_rec, (cc) * sizeof(struct hufd_chunk_rec))                                                               \
     X(d_states, (ci) * sizeof(struct hufd_dec_item_state))                                                             \
     /* the list counters as the launch's last kernel found them, one arena cut (256 bytes) in front of the records:    \
@@ -2482,6 +2483,7 @@ static void dec_plan_launch_args(
     a.tail_entry = p->d_tail_entry;
     a.chunk_entry = p->d_chunk_entry;
     a.chunk_base = p->d_chunk_base;
+    a.emit_rec = p->d_emit_rec;
     a.chunk_rec = p->d_chunk_rec;
     a.side_stream = p->engine->side_stream;
     a.fork_event = p->engine->fork_event;

@@ -159,6 +159,7 @@ struct aws_huffman_amd_decode_plan {
     uint32_t *d_tail_entry;
     uint32_t *d_chunk_entry;
     uint64_t *d_chunk_base;
+    struct hufd_emit_rec *d_emit_rec; /* [cap_chunks] written by every launch's scan stage, read by its emit stage */
     struct hufd_chunk_rec *d_chunk_rec;
     struct aws_huffman_amd_plan_stats stats; /* how the items are taken (aws_huffman_amd_decode_plan_stats) */
     void *d_plan_scratch; /* of a plan made on the device (hufk_plan_scratch_bytes) */
