@@ -15,7 +15,8 @@
  *
  * The same kernel has a second body, chosen by a launch argument: the hot pass of the block index (index_block_bits.hpp,
  * hufk_block_bits below), which reads the same bytes the same way and looks code lengths up where this one counts -- and a
- * third, the same pass over the items of a batch (index_batch_bits, hufk_batch_block_bits).
+ * third, the same pass over the items of a batch (index_batch_bits, hufk_batch_block_bits).  The fourth counts again: the
+ * symbols of the items of an encode plan, into the same histogram (count_plan_items, hufk_plan_symbol_counts).
  */
 #include "kernels_common.hpp"
 #include "index_block_bits.hpp"
@@ -55,6 +56,117 @@ __device__ __forceinline__ void count_flush(u32 *tab, u64 *counts) {
     }
 }
 
+/* the histogram cleared, behind a barrier */
+__device__ __forceinline__ void count_clear(u32 *tab) {
+    const u32 t = threadIdx.x;
+    if (t < 256) {
+        uint4 *row = reinterpret_cast<uint4 *>(tab + t * kCountCopies);
+#pragma unroll
+        for (u32 i = 0; i < kCountCopies / 4; ++i) {
+            row[i] = uint4{0u, 0u, 0u, 0u};
+        }
+    }
+    __syncthreads();
+}
+
+constexpr u32 kCountWaves = kCountThreads / kWave;
+constexpr u32 kCountWaveStepBytes = kWave * 16u * kCountUnroll;            /* what a wave reads of its span a step: 4 KiB */
+constexpr u32 kCountSpanSteps = HUFD_ENC_SEG_BYTES / kCountWaveStepBytes;  /* ... so the longest span takes four */
+constexpr u32 kCountLaneStepBytes = 16u * kCountUnroll;                    /* what a lane reads of its item a step: 64 bytes */
+static_assert(HUFD_ENC_SOLO_MANY_BYTES <= HUFD_ENC_SEG_BYTES, "a wave's item is no longer than a segment");
+
+/*
+ * The fourth body: the symbols of the current items of an encode plan (aws_huffman_amd_encode_plan_symbol_counts), into the
+ * same histogram, flushed the same way.  The plan's own lists cover every item exactly once, so they are the work: a
+ * UNIT is one segment, one item a wave encodes (both: a span of at most 16 KiB, read by one wave, lane l the 16 bytes at
+ * 16 l of every KiB) or 64 items a thread encodes (a lane an item).  The grid's waves take the units in turns; a turn is
+ * round_steps steps, the same number in every wave of the launch -- what the plan's longest unit takes, known to the
+ * host -- so that the flush's barriers are met by all.  In a step a lane issues four 16-byte loads at any alignment, a
+ * workgroup reads at most kCountStepBytes as in the first body, and steps_per_flush means the same.  Only whole groups of
+ * 16 bytes inside a span are loaded; its last len % 16 bytes go one by one, and nothing behind it is read.
+ */
+__device__ __forceinline__ void count_plan_items(const index_job &job, u64 *counts, u64 steps_per_flush) {
+    u32 *tab = reinterpret_cast<u32 *>(dyn_lds);
+    count_clear(tab);
+    const u32 t = threadIdx.x;
+    const u32 lane = t & (kWave - 1);
+    u32 *copy = tab + (t & (kCountCopies - 1));
+    /* (units, and the steps between two flushes, are numbered in 32 bits: the host sees to it -- fewer scalar registers) */
+    const u32 n_spans = job.n_segs + job.n_solo;
+    const u32 n_units = n_spans + (job.n_tiny + kWave - 1) / kWave;
+    const u32 round_steps = job.round_steps, per_flush = (u32)steps_per_flush;
+    const u32 rounds = (n_units + gridDim.x * kCountWaves - 1) / (gridDim.x * kCountWaves);
+    u32 steps = 0;
+    /* (the two loops' trips are the same in every thread of a workgroup: the barriers below are uniform) */
+    for (u32 r = 0; r < rounds; ++r) {
+        const u32 unit = (r * gridDim.x + blockIdx.x) * kCountWaves + wave_uniform(t / kWave);
+        const u8 *src = job.in;
+        u32 len = 0, at = 0;                                                     /* the span, and where this lane starts in it */
+        u32 load_stride = kWave * 16u, step_stride = kCountWaveStepBytes;        /* a wave's span */
+        if (unit < job.n_segs) {
+            const hufd_enc_seg *seg = job.segs + unit;
+            src += wave_uniform64(seg->in_off);
+            len = wave_uniform(seg->len);
+            at = lane * 16u;
+        } else if (unit < n_spans) {
+            const hufd_enc_item *item = job.items + wave_uniform(job.solo[unit - job.n_segs]);
+            src += wave_uniform64(item->in_off);
+            len = wave_uniform((u32)item->in_len);
+            at = lane * 16u;
+        } else if (unit < n_units) {
+            const u32 k = (unit - n_spans) * kWave + lane;
+            load_stride = 16u;
+            step_stride = kCountLaneStepBytes;
+            if (k < job.n_tiny) {
+                const hufd_enc_item *item = job.items + job.tiny[k];
+                src += item->in_off;
+                len = (u32)item->in_len;
+            }
+        }
+        /* the span's last len % 16 symbols, one by one, by the lane whose group they are (of a wave's span: the one that
+         * starts there in its KiB; of a lane's item: its own) -- in front of the turn's steps, fifteen symbols at the most:
+         * a counter sees them on top of what steps_per_flush lets it see, and has the room */
+        const u32 whole = len & ~15u;
+        if (whole != len && (whole & (load_stride - 1u)) == at) {
+            for (u32 a = whole; a < len; ++a) {
+                atomicAdd(&copy[(u32)src[a] * kCountCopies], 1u);
+            }
+        }
+        for (u32 s = 0; s < round_steps; ++s, at += step_stride) {
+            if (steps == per_flush) {
+                __syncthreads();
+                count_flush(tab, counts);
+                __syncthreads();
+                steps = 0;
+            }
+            ++steps;
+            uint4 v[kCountUnroll];
+            bool ok[kCountUnroll];
+#pragma unroll
+            for (u32 u = 0; u < kCountUnroll; ++u) {
+                const u32 a = at + u * load_stride;
+                ok[u] = a < whole;
+                v[u] = uint4{0u, 0u, 0u, 0u};
+                if (ok[u]) {
+                    const unaligned_uint4 w = *reinterpret_cast<const unaligned_uint4 *>(src + a);
+                    v[u] = uint4{w.x, w.y, w.z, w.w};
+                }
+            }
+#pragma unroll
+            for (u32 u = 0; u < kCountUnroll; ++u) {
+                if (ok[u]) {
+                    count_word(copy, v[u].x);
+                    count_word(copy, v[u].y);
+                    count_word(copy, v[u].z);
+                    count_word(copy, v[u].w);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    count_flush(tab, counts);
+}
+
 /* body: n_vec 16-byte vectors at a 16-byte aligned address; head / tail: the bytes around it (workgroup 0's);
  * steps_per_flush: steps of kCountStepBytes a workgroup reads between two flushes (>= 1) */
 __global__ __launch_bounds__(kCountThreads) void count_kernel(
@@ -68,16 +180,13 @@ __global__ __launch_bounds__(kCountThreads) void count_kernel(
         }
         return;
     }
+    if (index.items) {
+        count_plan_items(index, counts, steps_per_flush);
+        return;
+    }
     u32 *tab = reinterpret_cast<u32 *>(dyn_lds);
     const u32 t = threadIdx.x;
-    if (t < 256) {
-        uint4 *row = reinterpret_cast<uint4 *>(tab + t * kCountCopies);
-#pragma unroll
-        for (u32 i = 0; i < kCountCopies / 4; ++i) {
-            row[i] = uint4{0u, 0u, 0u, 0u};
-        }
-    }
-    __syncthreads();
+    count_clear(tab);
     u32 *copy = tab + (t & (kCountCopies - 1));
     if (blockIdx.x == 0) {
         if (t < head_len) {
@@ -144,6 +253,41 @@ int hufk_symbol_counts(const void *input, uint64_t length, uint64_t *counts, uin
         count_kernel, dim3(grid), dim3(kCountThreads), kCountLdsBytes, (hipStream_t)stream, in, (u32)head_len,
         reinterpret_cast<const uint4 *>(in + head_len), n_vec, in + head_len + n_vec * 16u, (u32)tail_len, counts, per_flush,
         index_job{});
+    return (int)hipGetLastError();
+}
+
+int hufk_plan_symbol_counts(
+    const struct hufd_enc_item *items, const struct hufd_enc_seg *segs, uint32_t n_segs, const uint32_t *solo, uint32_t n_solo,
+    const uint32_t *tiny, uint32_t n_tiny, uint64_t thread_limit, const void *input, uint64_t *counts, uint64_t flush_bytes,
+    void *stream) {
+    const u64 n_units = (u64)n_segs + n_solo + ((u64)n_tiny + kWave - 1) / kWave;
+    if (n_units == 0) {
+        return 0;
+    }
+    if ((n_units + 0xFFFFu) >> 32) { /* (64 TiB of segments: the kernel numbers the units of every turn in 32 bits) */
+        return (int)hipErrorInvalidValue;
+    }
+    index_job job{};
+    job.in = (const u8 *)input;
+    job.items = items;
+    job.segs = segs;
+    job.solo = solo;
+    job.tiny = tiny;
+    job.n_segs = n_segs;
+    job.n_solo = n_solo;
+    job.n_tiny = n_tiny;
+    /* a turn: the steps of a whole segment where a wave has a span, of the longest item a thread may have where a lane has one */
+    const u64 lane_steps = n_tiny ? (thread_limit + kCountLaneStepBytes - 1) / kCountLaneStepBytes : 0;
+    const u64 span_steps = n_segs || n_solo ? kCountSpanSteps : 0;
+    job.round_steps = (u32)(lane_steps > span_steps ? lane_steps : span_steps);
+    const u64 want = (n_units + kCountWaves - 1) / kCountWaves;
+    const uint32_t grid = hufk_host::persistent_grid(
+        count_kernel, kCountThreads, kCountLdsBytes, (uint32_t)(want < 0xFFFFFFFFull ? want : 0xFFFFFFFFull));
+    u64 per_flush = flush_bytes / kCountStepBytes; /* (a workgroup reads at most kCountStepBytes a step here too) */
+    per_flush = per_flush ? (per_flush < 0xFFFFFFFFull ? per_flush : 0xFFFFFFFFull) : 1;
+    hipLaunchKernelGGL(
+        count_kernel, dim3(grid), dim3(kCountThreads), kCountLdsBytes, (hipStream_t)stream, (const u8 *)nullptr, 0u,
+        (const uint4 *)nullptr, (u64)0, (const u8 *)nullptr, 0u, counts, per_flush, job);
     return (int)hipGetLastError();
 }
 

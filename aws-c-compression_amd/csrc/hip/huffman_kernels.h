@@ -222,6 +222,14 @@ int hufk_fill_splitmix64(void *dst, uint64_t len, uint64_t seed, void *stream);
 /* counts[b] += the bytes of input[0 .. length) equal to b, u64 agent-scope atomic adds (count_kernels.hip); flush_bytes:
  * what a workgroup reads at most between two flushes of its 32-bit LDS counts (rounded down to 32 KiB, at least that) */
 int hufk_symbol_counts(const void *input, uint64_t length, uint64_t *counts, uint64_t flush_bytes, void *stream);
+/* the same sums over the items of an encode plan, through the plan's own lists, which cover every item once: its segments,
+ * the items a wave encodes (solo) and the items a thread encodes (tiny; none of them longer than thread_limit), the last
+ * two as numbers of items[]; `input` is the base the items' in_off count from.  One launch, or none for a plan without
+ * items; the same adds, the same flush_bytes */
+int hufk_plan_symbol_counts(
+    const struct hufd_enc_item *items, const struct hufd_enc_seg *segs, uint32_t n_segs, const uint32_t *solo, uint32_t n_solo,
+    const uint32_t *tiny, uint32_t n_tiny, uint64_t thread_limit, const void *input, uint64_t *counts, uint64_t flush_bytes,
+    void *stream);
 /* Between the length pass and the encode pass of a packed launch (pack_kernels.hip): from the length pass's records
  * `lengths`, offsets[i] = the sum of round_up((total_bits + 7) / 8, align) of the items in front of i, offsets[n_items] the
  * total; packed[i] = items[i] with out_off = offsets[i] and out_cap = what of the item's rounded length lies in front of

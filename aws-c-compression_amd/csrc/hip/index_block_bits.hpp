@@ -44,19 +44,45 @@ constexpr u64 kIndexHole = 1ull << 63; /* on a tile's first entry, between this 
  * groups_per_block = block_symbols / 16.  inverse = ceil(2^32 / groups_per_block) for tiles of several blocks: the high
  * word of g * inverse is g / groups_per_block for every group of such a tile (g < 2^12, groups_per_block <= 2^10: the
  * error, below g / 2^32, stays below 1 / groups_per_block); 0 for tiles of one block, whose groups are all block 0's.
+ *
+ * index == nullptr and items != nullptr: the launch counts the symbols of a plan's items (count_plan_items,
+ * count_kernels.hip).  What only that body needs shares the words of what only the index needs, as in hufd_locate: the
+ * kernel holds every word of this argument in a scalar register, and more of them would cost the other bodies.  Its four
+ * small numbers lie on length and block_symbols, which the kernel loads at its entry for every body: on the four words
+ * behind them, which only the index loads, the build had 81 scalar registers -- one band of residency lost -- and has 78 so.
  */
 struct index_job {
-    const u64 *enc_table;
+    union {
+        const u64 *enc_table;
+        const u32 *tiny; /* (count) the plan's items a thread encodes: n_tiny numbers of items[] */
+    };
     const u8 *in;
-    u64 length, block_symbols;
+    union {
+        u64 length;
+        struct {
+            u32 n_segs, n_solo; /* (count) */
+        };
+    };
+    union {
+        u64 block_symbols;
+        struct {
+            u32 n_tiny, round_steps; /* (count) steps of a turn: what the plan's longest unit takes, see count_plan_items */
+        };
+    };
     u32 groups_per_block, inverse, tile_blocks, pad;
     u64 n_tiles, n_blocks;
     u64 *index;
     /* the index of a batch (index_batch_bits below; items == nullptr: one stream): `in` is the input base of the plan's
      * items, and length, n_tiles and n_blocks are not the host's to know -- the directory and tile_first say them */
     const hufd_enc_item *items;
-    const u64 *directory;  /* [n_items + 1][2]: the blocks in front of an item, its symbols */
-    const u64 *tile_first; /* [n_items + 1]: the tiles in front of an item */
+    union {
+        const u64 *directory;     /* [n_items + 1][2]: the blocks in front of an item, its symbols */
+        const hufd_enc_seg *segs; /* (count) the plan's segments: n_segs */
+    };
+    union {
+        const u64 *tile_first; /* [n_items + 1]: the tiles in front of an item */
+        const u32 *solo;       /* (count) the plan's items a wave encodes: n_solo numbers of items[] */
+    };
     u64 wave_bytes, capacity;
     u32 n_items, wave_inverse; /* ceil(2^32 / groups_per_block) where that is at most 2^10, else 0 */
 };

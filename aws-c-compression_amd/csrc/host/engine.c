@@ -13,6 +13,7 @@
 #include <aws/compression/huffman_amd_fit.h>
 #include <aws/compression/huffman_amd_index.h>
 #include <aws/compression/huffman_amd_packed.h>
+#include <aws/compression/huffman_amd_plan_counts.h>
 #include <aws/compression/huffman_amd_ranges.h>
 
 #include <assert.h>
@@ -3955,6 +3956,32 @@ int aws_huffman_amd_symbol_counts(int device, const void *device_input, uint64_t
     if (!err) {
         const uint64_t asked = __atomic_load_n(&s_count_flush_bytes, __ATOMIC_RELAXED);
         err = hufk_symbol_counts(device_input, length, device_counts, asked ? asked : (1ull << 30), stream);
+    }
+    return err ? raise_hip(err) : AWS_OP_SUCCESS;
+}
+
+/* the same sums over the current items of an encode plan (huffman_amd_plan_counts.h): the plan's own lists are the work, so
+ * nothing is made for the call -- no scratch, no wait -- and nothing of the plan is written */
+int aws_huffman_amd_encode_plan_symbol_counts(
+    struct aws_huffman_amd_encode_plan *p, const void *device_input, uint64_t *device_counts, void *stream) {
+    if (hufs_device_count() <= 0) {
+        return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION); /* no GPU: there is no CPU path */
+    }
+    if (!p || !device_counts || ((uintptr_t)device_counts & 7u) || (p->n_items && !device_input)) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    if (p->n_items == 0) {
+        return AWS_OP_SUCCESS;
+    }
+    struct aws_huffman_amd_engine *eng = p->engine;
+    ON_DEVICE(eng->device);
+    const uint64_t asked = __atomic_load_n(&s_count_flush_bytes, __ATOMIC_RELAXED);
+    int err = hufk_plan_symbol_counts(
+        p->d_items, p->d_segs, p->n_segs, p->d_solo, p->n_solo, p->d_tiny, p->n_tiny, p->stats.thread_limit, device_input,
+        device_counts, asked ? asked : (1ull << 30), stream ? stream : eng->stream);
+    if (!err) {
+        /* (the plan's records are read on this stream: whoever gets its arrays next waits, as for a launch) */
+        err = plan_mark_done(&p->done_event, &p->done_on_engine_stream, eng, stream);
     }
     return err ? raise_hip(err) : AWS_OP_SUCCESS;
 }

@@ -9,7 +9,8 @@
  *   aws_huffman_amd_encode_plan_new(&plan, engine, items, n);                    (once: good for every fit)
  *   per batch, all on `stream`:
  *     hipMemsetAsync(d_counts, 0, 256 * sizeof(uint64_t), stream);
- *     aws_huffman_amd_symbol_counts(-1, d_input, length, d_counts, stream);
+ *     aws_huffman_amd_encode_plan_symbol_counts(plan, d_input, d_counts, stream);   (huffman_amd_plan_counts.h: the plan's
+ *                                                  items, whatever they cover; aws_huffman_amd_symbol_counts where they tile a range)
  *     aws_huffman_amd_engine_fit_counts(engine, d_counts, d_num_bits, d_status, stream);
  *     aws_huffman_amd_encode_plan_launch_packed(plan, d_input, d_output, capacity, d_offsets, 1, stream);
  *   the receiver, given the 256 bytes of d_num_bits beside the packed buffer and its offsets:
