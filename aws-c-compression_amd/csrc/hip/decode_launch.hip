@@ -578,7 +578,7 @@ static int decode_launch_stages(const struct hufk_decode_args *a, const struct h
          * that write there */
         const int e = hufk_unpack_offsets(
             a->items, a->results, a->n_items, pk->tile_items, pk->align, pk->capacity, pk->tile_sums, pk->offsets, pk->items,
-            pk->summary, a->chunk_rec, a->n_chunks, pk->chunk_rec, st);
+            pk->summary, a->chunk_rec, a->n_chunks, pk->chunk_rec, pk->stored_rec, st);
         if (e) {
             return e;
         }
@@ -596,6 +596,14 @@ static int decode_launch_stages(const struct hufk_decode_args *a, const struct h
     }
     if (a->n_chunks) {
         hufk_host::decode_emit_stage(a, st, state);
+    }
+    if (pk && pk->stored_rec) {
+        /* the items stored raw: copied to their places, their records rewritten, behind every kernel that writes records */
+        const int e = hufk_stored_copy_decode(
+            pk->stored_rec, pk->stored_tile_first, pk->stored_tiles, a->n_items, pk->items, a->results, a->d_in, a->d_out, st);
+        if (e) {
+            return e;
+        }
     }
     stage_mark(a->stage_events, 3, st);
     return (int)hipGetLastError();

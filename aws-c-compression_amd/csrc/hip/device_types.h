@@ -246,6 +246,7 @@ struct hufd_emit_rec {
 #define HUFD_ITEMS_SYMBOL_RANGES 5u
 #define HUFD_ITEMS_ITEM_BLOCK_RANGES 6u
 #define HUFD_ITEMS_ITEM_SYMBOL_RANGES 7u
+#define HUFD_ITEMS_PACKED_STORED_INPUT 8u
 /* a range of whole blocks of an indexed stream, as the public header lays it out (struct aws_huffman_amd_block_range) */
 struct hufd_block_range {
     uint64_t first_block;
@@ -311,6 +312,10 @@ struct hufd_item_source {
      * located_bits[2 i] and [2 i + 1] as bits from the packed buffer's first byte (HUFD_NO_BIT: not found -- also for an item
      * whose directory records cannot be); batch_directory, batch_items, packed_offsets / packed_lengths as above */
     const struct hufd_item_symbol_range *item_symbol_ranges;
+    /* a packed input with items stored raw (decode, huffman_amd_stored.h): packed_offsets / packed_lengths as above, and
+     * packed_stored[i] = 1 for an item whose bytes are its symbols -- no encoded bytes for the decode kernels: the plan copies
+     * it (stored_copy.hpp) -- or 0; any other byte: no plan */
+    const uint8_t *packed_stored;
 };
 
 /*

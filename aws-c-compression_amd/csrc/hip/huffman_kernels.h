@@ -157,6 +157,10 @@ struct hufk_decode_pack {
     uint64_t *summary;   /* [2]: the total, the largest rounded count */
     struct hufd_dec_item *items;      /* [n_items] the second record array: args->items with out_off / out_cap rewritten */
     struct hufd_chunk_rec *chunk_rec; /* [n_chunks] ... and args->chunk_rec with the same */
+    /* a plan with stored items (huffman_amd_stored.h; NULL: none): their records, the tiles of the long ones */
+    const uint64_t *stored_rec;        /* [n_items][2] */
+    const uint64_t *stored_tile_first; /* [n_items + 1] */
+    uint64_t stored_tiles;
 };
 int hufk_decode_launch_packed(const struct hufk_decode_args *args, const struct hufk_decode_pack *pack, void *stream);
 /* a plan of items that are all one thread's work: the kernels' item records and the list of such items (= all of them) from
@@ -248,7 +252,41 @@ int hufk_unpack_blank(const struct hufd_dec_item *items, uint32_t n_items, struc
 int hufk_unpack_offsets(
     const struct hufd_dec_item *items, const struct hufd_dec_result *counts, uint32_t n_items, uint32_t tile_items, uint64_t align,
     uint64_t capacity, uint64_t *tile_sums, uint64_t *offsets, struct hufd_dec_item *packed, uint64_t *summary,
-    const struct hufd_chunk_rec *chunk_rec, uint32_t n_chunks, struct hufd_chunk_rec *packed_rec, void *stream);
+    const struct hufd_chunk_rec *chunk_rec, uint32_t n_chunks, struct hufd_chunk_rec *packed_rec, const uint64_t *stored_rec,
+    void *stream);
+/* Items stored raw in a packed batch (huffman_amd_stored.h; pack_kernels.hip, stored_copy.hpp).
+ *   _pack_offsets_stored  hufk_pack_offsets with len_i = in_len_i for a stored item (in_len_i > 0, no carried bits, a coded
+ *                         length that is no shorter); also stored[i] = 0 / 1, packed[i].out_cap = 0 for a stored item,
+ *                         summary[2] = summary[3] = 0 (summary: four words)
+ *   _stored_copy_encode   behind the encode pass over `packed`: the stored items' bytes to output + offsets[i], as far as they
+ *                         lie in front of `capacity`, distributed by the plan's lists as hufk_plan_symbol_counts is; their
+ *                         result records; counts[0] += the stored items, counts[1] += their bytes
+ *   _stored_records       a receiver's records: stored_rec[i] = {offsets[i], the packed length of a stored item or
+ *                         HUFK_NOT_STORED}, from arrays the planner's pass has checked (lengths NULL: up to the next offset)
+ *   _stored_tiles         tile_first[0 .. n_items]: the tiles of tile_bytes in front of each item, none for an item that is
+ *                         not stored or shorter than wave_bytes; tile_sums: 2 * hufk_pack_tiles() words
+ *   hufk_unpack_offsets   with stored_rec != NULL: sym_i = the packed length of a stored item
+ *   _stored_copy_decode   behind the emit stage: every stored item whose placed record has room for it copied to its place, a
+ *                         workgroup a tile or a wave an item; the stored items' result records */
+#define HUFK_NOT_STORED 0xFFFFFFFFFFFFFFFFull
+#define HUFK_STORED_TILE_BYTES 16384u
+#define HUFK_STORED_WAVE_BYTES 4096u
+int hufk_pack_offsets_stored(
+    const struct hufd_enc_item *items, const struct hufd_enc_result *lengths, uint32_t n_items, uint32_t tile_items, uint64_t align,
+    uint64_t capacity, uint64_t *tile_sums, uint64_t *offsets, struct hufd_enc_item *packed, uint64_t *summary, uint8_t *stored,
+    void *stream);
+int hufk_stored_copy_encode(
+    const struct hufd_enc_item *items, uint32_t n_items, const struct hufd_enc_seg *segs, uint32_t n_segs, const uint32_t *solo,
+    uint32_t n_solo, const uint32_t *tiny, uint32_t n_tiny, const uint8_t *stored, const uint64_t *offsets, uint64_t capacity,
+    const void *input, void *output, struct hufd_enc_result *results, uint64_t *counts, void *stream);
+int hufk_stored_records(
+    const uint64_t *offsets, const uint64_t *lengths, const uint8_t *stored, uint32_t n_items, uint64_t *stored_rec, void *stream);
+int hufk_stored_tiles(
+    const uint64_t *stored_rec, uint32_t n_items, uint32_t tile_items, uint64_t tile_bytes, uint64_t wave_bytes, uint64_t *tile_sums,
+    uint64_t *tile_first, void *stream);
+int hufk_stored_copy_decode(
+    const uint64_t *stored_rec, const uint64_t *tile_first, uint64_t n_tiles, uint32_t n_items, const struct hufd_dec_item *placed,
+    struct hufd_dec_result *results, const void *input, void *output, void *stream);
 /* A coder fitted on the device (fit_kernels.hip, huffman_amd_fit.h): ONE launch of one workgroup writes enc_table[256] and
  * dec_lut[1 << max_bits] -- from 256 counts (from_lengths 0: package-merge lengths in min_bits .. max_bits for all 256
  * symbols, also left in num_bits_out where that is not NULL), or from 256 lengths (from_lengths 1) -- and *status (NULL: not

@@ -119,6 +119,19 @@ constexpr u32 kPackTiles = 4;
  * registers in vector lanes, with builds of its own four (no scratch memory either way). */
 constexpr u32 kPackIndexed = 5;
 constexpr u64 kPackMaxBlocks = 1ull << 32; /* what an item counts at most: no sum of 2^32 items overflows */
+/* Two kinds with items stored raw (huffman_amd_stored.h), builds of the bodies of their own (STORED, the kind a constant in
+ * them) for the reason above.  kPackStored, the offsets of aws_huffman_amd_encode_plan_launch_packed_stored: kind 0 with
+ *   len_i = stored_i ? in_len_i : ceil(total_bits_i / 8),   stored_i = in_len_i > 0 && ovf_bits_i == 0 && ceil(..) >= in_len_i
+ * -- the plan's item records travel beside the length pass's records --; the offsets pass also writes the caller's flag, gives
+ * a stored item no room in the second record array (the encode pass writes nothing for it: stored_copy.hpp copies it
+ * behind that pass) and clears the two words the copy counts the stored items in.  kPackUnstored, the offsets of a packed
+ * decode launch of a plan with stored items: kind 1 with sym_i = the packed length of a stored item, as the plan's stored
+ * records {source offset, length or kPackNotStored} say.  A ninth, kPackStoredTiles, a build of the batch kinds: the tiles
+ * the copy cuts the long stored items of such a plan into, from the same records, scanned into tile_first[0 .. n_items]. */
+constexpr u32 kPackStored = 6;
+constexpr u32 kPackUnstored = 7;
+constexpr u32 kPackStoredTiles = 8;
+constexpr u64 kPackNotStored = HUFK_NOT_STORED;
 
 struct pack_batch {
     u64 block_symbols, tile_blocks, wave_bytes; /* kPackBlocks, kPackTiles */
@@ -126,18 +139,39 @@ struct pack_batch {
     u64 *index;       /* kPackBlocks: the caller's index (index[0] = 0 is written where the batch has no block) */
     u32 *status;      /* kPackBlocks: the caller's status word, or NULL */
     const u64 *count; /* kPackIndex: the batch's blocks, counted on the device (NULL: n_items holds); kPackIndexed: the same word */
-    const u64 *directory; /* kPackIndexed: [n_items + 1][2], and `index` scanned, `capacity` its entries */
+    const u64 *directory; /* kPackIndexed: [n_items + 1][2], and `index` scanned, `capacity` its entries;
+                           * kPackUnstored, kPackStoredTiles: the plan's stored records, [n_items][2] */
+    const void *second;   /* kPackStored, kPackUnstored: the plan's item records (what `lengths` is not) */
+    u8 *stored;           /* kPackStored: the caller's flags */
 };
+
+/* the rule of huffman_amd_stored.h: a tie is stored, carried bits and empty items never */
+__device__ __forceinline__ bool pack_item_stored(const hufd_enc_item *item, u64 coded_len) {
+    return item->in_len > 0 && item->ovf_bits == 0 && coded_len >= item->in_len;
+}
 
 /* whether a batch of `blocks` blocks has an index in `capacity` entries (blocks + 1 of them, blocks below 2^32) */
 __device__ __forceinline__ bool pack_batch_fits(u64 blocks, u64 capacity) {
     return blocks < capacity && blocks < kPackMaxBlocks;
 }
 
-template <bool BATCH, bool INDEXED = false>
+template <bool BATCH, bool INDEXED = false, u32 STORED = 0>
 __device__ __forceinline__ u64 pack_length(const void *lengths, u32 decode, u64 i, const pack_batch &batch) {
+    if (STORED == kPackStored) {
+        const hufd_enc_item *item = reinterpret_cast<const hufd_enc_item *>(batch.second) + i;
+        const u64 coded = pack_encode::length(reinterpret_cast<const pack_encode::measured *>(lengths), i);
+        return pack_item_stored(item, coded) ? item->in_len : coded;
+    }
+    if (STORED == kPackUnstored) {
+        const u64 raw = batch.directory[2 * i + 1];
+        return raw != kPackNotStored ? raw : pack_decode::length(reinterpret_cast<const pack_decode::measured *>(lengths), i);
+    }
     if (decode == kPackIndex) {
         return reinterpret_cast<const u64 *>(lengths)[i] & ~kPackIndexHole;
+    }
+    if (BATCH && decode == kPackStoredTiles) { /* (`lengths`: the stored records; tile_blocks: a tile's bytes) */
+        const u64 len = reinterpret_cast<const u64 *>(lengths)[2 * i + 1];
+        return len == kPackNotStored || len < batch.wave_bytes ? 0 : (len + batch.tile_blocks - 1) / batch.tile_blocks;
     }
     if (INDEXED) {
         if (!pack_batch_fits(*batch.count, batch.capacity)) { /* (the same in every thread of the launch) */
@@ -165,10 +199,10 @@ __device__ __forceinline__ u64 pack_most(const void *lengths, u32 decode, u64 i,
     return decode == kPackIndex ? reinterpret_cast<const u64 *>(lengths)[i] : reserved;
 }
 
-template <bool BATCH, bool INDEXED = false>
+template <bool BATCH, bool INDEXED = false, u32 STORED = 0>
 __device__ __forceinline__ u64 pack_reserved(const void *lengths, u32 decode, u64 i, u64 align_mask, const pack_batch &batch) {
-    const u64 len = pack_length<BATCH, INDEXED>(lengths, decode, i, batch);
-    return BATCH && !INDEXED && decode >= kPackBlocks ? len : (len + align_mask) & ~align_mask;
+    const u64 len = pack_length<BATCH, INDEXED, STORED>(lengths, decode, i, batch);
+    return BATCH && !INDEXED && !STORED && decode >= kPackBlocks ? len : (len + align_mask) & ~align_mask;
 }
 
 /* the entries a scan has: for the index of a batch (`count` != NULL) what the device says, 0 where there is nothing to scan
@@ -235,7 +269,7 @@ __device__ __forceinline__ u64 pack_block_exclusive_sum(u64 v, u64 *slots, u64 &
 }
 
 /* tile_sums[2 b] = the sum of reserved_i over tile b, tile_sums[2 b + 1] = the largest of them */
-template <bool BATCH, bool INDEXED = false>
+template <bool BATCH, bool INDEXED = false, u32 STORED = 0>
 __device__ __forceinline__ void pack_tile_sums_body(
     const void *lengths, u32 decode, u32 n_items, u32 tile_items, u64 align_mask, u64 *tile_sums, const pack_batch &batch) {
     u64 *slots = reinterpret_cast<u64 *>(dyn_lds);
@@ -247,7 +281,7 @@ __device__ __forceinline__ void pack_tile_sums_body(
     const u64 hi = lo + tile_items < n_items ? lo + tile_items : n_items;
     u64 sum = 0, most = 0;
     for (u64 i = lo + threadIdx.x; i < hi; i += kPackThreads) {
-        const u64 r = pack_reserved<BATCH, INDEXED>(lengths, decode, i, align_mask, batch);
+        const u64 r = pack_reserved<BATCH, INDEXED, STORED>(lengths, decode, i, align_mask, batch);
         const u64 m = pack_most(lengths, decode, i, r);
         sum += r;
         most = m > most ? m : most;
@@ -260,7 +294,7 @@ __device__ __forceinline__ void pack_tile_sums_body(
 }
 
 /* offsets[0 .. n_items], packed[0 .. n_items), summary[0] = the total, summary[1] = the largest reserved length */
-template <bool BATCH, bool INDEXED = false>
+template <bool BATCH, bool INDEXED = false, u32 STORED = 0>
 __device__ __forceinline__ void pack_offsets_body(
     const void *items, const void *lengths, u32 decode, u32 n_items, u32 tile_items, u64 align_mask, u64 capacity,
     const u64 *tile_sums, u64 *offsets, void *packed, u64 *summary, const pack_batch &batch) {
@@ -282,12 +316,26 @@ __device__ __forceinline__ void pack_offsets_body(
     u64 mine = 0; /* the largest reserved length this thread met */
     for (u64 round = lo; round < hi; round += kPackThreads) { /* (the same trips in every thread: the scan has barriers) */
         const u64 i = round + threadIdx.x;
-        const u64 reserved = i < hi ? pack_reserved<BATCH, INDEXED>(lengths, decode, i, align_mask, batch) : 0;
+        const u64 reserved = i < hi ? pack_reserved<BATCH, INDEXED, STORED>(lengths, decode, i, align_mask, batch) : 0;
         const u64 marked = i < hi ? pack_most(lengths, decode, i, reserved) : 0;
         u64 total = 0;
         const u64 off = at + pack_block_exclusive_sum(reserved, slots, total);
         if (i < hi) {
-            if (decode == 1) {
+            if (STORED == kPackStored) {
+                const pack_encode::item *from = reinterpret_cast<const pack_encode::item *>(batch.second) + i;
+                pack_encode::item *to = reinterpret_cast<pack_encode::item *>(packed) + i;
+                const bool stored =
+                    pack_item_stored(from, pack_encode::length(reinterpret_cast<const pack_encode::measured *>(lengths), i));
+                pack_encode::place(from, to, off, 0, reserved, capacity);
+                if (stored) {
+                    to->out_cap = 0;
+                }
+                batch.stored[i] = stored ? 1u : 0u;
+            } else if (STORED == kPackUnstored) {
+                pack_decode::place(
+                    reinterpret_cast<const pack_decode::item *>(batch.second) + i, reinterpret_cast<pack_decode::item *>(packed) + i, off,
+                    pack_length<BATCH, INDEXED, STORED>(lengths, decode, i, batch), reserved, capacity);
+            } else if (decode == 1) {
                 pack_decode::place(
                     reinterpret_cast<const pack_decode::item *>(items) + i, reinterpret_cast<pack_decode::item *>(packed) + i, off,
                     pack_length<BATCH>(lengths, decode, i, batch), reserved, capacity);
@@ -326,7 +374,7 @@ __device__ __forceinline__ void pack_offsets_body(
                 return;
             }
             offsets[n_items] = at;
-            if (BATCH && decode == kPackTiles) {
+            if (BATCH && (decode == kPackTiles || decode == kPackStoredTiles)) {
                 return;
             }
             if (decode == kPackIndex) {
@@ -337,6 +385,10 @@ __device__ __forceinline__ void pack_offsets_body(
             } else {
                 summary[0] = at;
                 summary[1] = mine > most ? mine : most;
+                if (STORED == kPackStored) { /* (the stored items and their bytes: the copy behind the encode pass adds them) */
+                    summary[2] = 0;
+                    summary[3] = 0;
+                }
             }
         }
     }
@@ -354,17 +406,25 @@ __global__ __launch_bounds__(kPackThreads) void pack_offsets_kernel(
         items, lengths, decode, n_items, tile_items, align_mask, capacity, tile_sums, offsets, packed, summary, pack_batch{});
 }
 
+#include "stored_copy.hpp"
+
 /* what unpack_records_kernel is given where it runs a pass of the scan with the batch kinds (pass 0: it does not) */
 struct pack_scan {
-    u32 pass; /* 1: the tile sums, 2: the offsets */
-    u32 decode, n_items, tile_items;
-    const void *lengths;
-    u64 *tile_sums, *offsets, *summary;
-    pack_batch batch;
-    /* kPackIndexed alone (0 and NULL for every other kind): what kind 0 is given as arguments of pack_offsets_kernel -- the
-     * items are `lengths` */
-    u64 align_mask, out_capacity;
-    void *packed;
+    u32 pass; /* 1: the tile sums, 2: the offsets, 3: the copy of items stored raw (stored_copy.hpp) */
+    u32 unused;
+    union { /* (a launch is a pass of the scan or the copy, never both: the copy's job shares the scan's words) */
+        struct {
+            u32 decode, n_items, tile_items;
+            const void *lengths;
+            u64 *tile_sums, *offsets, *summary;
+            pack_batch batch;
+            /* kPackIndexed, kPackStored, kPackUnstored (0 and NULL for every other kind): what kinds 0 and 1 are given as
+             * arguments of pack_offsets_kernel -- the items are `lengths` (kPackIndexed) or batch.second */
+            u64 align_mask, out_capacity;
+            void *packed;
+        };
+        stored_job stored; /* pass 3 */
+    };
 };
 
 /* The records of a packed decode launch that are not the scan's to write, a thread each (ONE kernel for both uses):
@@ -375,10 +435,20 @@ struct pack_scan {
 __global__ __launch_bounds__(kPackThreads) void unpack_records_kernel(
     const hufd_dec_item *items, hufd_dec_item *packed, const hufd_chunk_rec *chunk_rec, hufd_chunk_rec *packed_rec, u32 n,
     pack_scan scan) {
+    if (scan.pass == 3) {
+        stored_copy_body(scan.stored);
+        return;
+    }
     if (scan.pass == 1) {
         if (scan.decode == kPackIndexed) {
             pack_tile_sums_body<true, true>(
                 scan.lengths, kPackIndexed, scan.n_items, scan.tile_items, scan.align_mask, scan.tile_sums, scan.batch);
+        } else if (scan.decode == kPackStored) {
+            pack_tile_sums_body<true, false, kPackStored>(
+                scan.lengths, kPackStored, scan.n_items, scan.tile_items, scan.align_mask, scan.tile_sums, scan.batch);
+        } else if (scan.decode == kPackUnstored) {
+            pack_tile_sums_body<true, false, kPackUnstored>(
+                scan.lengths, kPackUnstored, scan.n_items, scan.tile_items, scan.align_mask, scan.tile_sums, scan.batch);
         } else {
             pack_tile_sums_body<true>(scan.lengths, scan.decode, scan.n_items, scan.tile_items, 0, scan.tile_sums, scan.batch);
         }
@@ -388,6 +458,14 @@ __global__ __launch_bounds__(kPackThreads) void unpack_records_kernel(
         if (scan.decode == kPackIndexed) {
             pack_offsets_body<true, true>(
                 scan.lengths, scan.lengths, kPackIndexed, scan.n_items, scan.tile_items, scan.align_mask, scan.out_capacity,
+                scan.tile_sums, scan.offsets, scan.packed, scan.summary, scan.batch);
+        } else if (scan.decode == kPackStored) {
+            pack_offsets_body<true, false, kPackStored>(
+                scan.batch.second, scan.lengths, kPackStored, scan.n_items, scan.tile_items, scan.align_mask, scan.out_capacity,
+                scan.tile_sums, scan.offsets, scan.packed, scan.summary, scan.batch);
+        } else if (scan.decode == kPackUnstored) {
+            pack_offsets_body<true, false, kPackUnstored>(
+                scan.batch.second, scan.lengths, kPackUnstored, scan.n_items, scan.tile_items, scan.align_mask, scan.out_capacity,
                 scan.tile_sums, scan.offsets, scan.packed, scan.summary, scan.batch);
         } else {
             pack_offsets_body<true>(
@@ -460,6 +538,16 @@ int pack_batch_launch(
             (const hufd_dec_item *)nullptr, (hufd_dec_item *)nullptr, (const hufd_chunk_rec *)nullptr, (hufd_chunk_rec *)nullptr, 0u, scan);
     }
     return (int)hipGetLastError();
+}
+
+/* a launch of the bodies of stored_copy.hpp */
+void stored_launch(const stored_job &job, uint32_t blocks, hipStream_t st) {
+    pack_scan scan{};
+    scan.pass = 3;
+    scan.stored = job;
+    hipLaunchKernelGGL(
+        unpack_records_kernel, dim3(blocks), dim3(kPackThreads), kPackLdsBytes, st, (const hufd_dec_item *)nullptr, (hufd_dec_item *)nullptr,
+        (const hufd_chunk_rec *)nullptr, (hufd_chunk_rec *)nullptr, 0u, scan);
 }
 
 } /* namespace */
@@ -540,6 +628,33 @@ int hufk_pack_offsets_indexed(
         items, kPackIndexed, n_items, tile_items, tile_sums, offsets, summary, batch, (hipStream_t)stream, align, capacity, packed);
 }
 
+int hufk_pack_offsets_stored(
+    const struct hufd_enc_item *items, const struct hufd_enc_result *lengths, uint32_t n_items, uint32_t tile_items, uint64_t align,
+    uint64_t capacity, uint64_t *tile_sums, uint64_t *offsets, struct hufd_enc_item *packed, uint64_t *summary, uint8_t *stored,
+    void *stream) {
+    if (n_items == 0 || tile_items == 0) {
+        return 0;
+    }
+    pack_batch batch{};
+    batch.second = items;
+    batch.stored = stored;
+    return pack_batch_launch(
+        lengths, kPackStored, n_items, tile_items, tile_sums, offsets, summary, batch, (hipStream_t)stream, align, capacity, packed);
+}
+
+int hufk_stored_tiles(
+    const uint64_t *stored_rec, uint32_t n_items, uint32_t tile_items, uint64_t tile_bytes, uint64_t wave_bytes, uint64_t *tile_sums,
+    uint64_t *tile_first, void *stream) {
+    if (n_items == 0 || tile_items == 0) {
+        return 0;
+    }
+    pack_batch batch{};
+    batch.block_symbols = 1;
+    batch.tile_blocks = tile_bytes;
+    batch.wave_bytes = wave_bytes;
+    return pack_batch_launch(stored_rec, kPackStoredTiles, n_items, tile_items, tile_sums, tile_first, nullptr, batch, (hipStream_t)stream);
+}
+
 int hufk_unpack_blank(const struct hufd_dec_item *items, uint32_t n_items, struct hufd_dec_item *packed, void *stream) {
     if (n_items == 0) {
         return 0;
@@ -553,15 +668,100 @@ int hufk_unpack_blank(const struct hufd_dec_item *items, uint32_t n_items, struc
 int hufk_unpack_offsets(
     const struct hufd_dec_item *items, const struct hufd_dec_result *counts, uint32_t n_items, uint32_t tile_items, uint64_t align,
     uint64_t capacity, uint64_t *tile_sums, uint64_t *offsets, struct hufd_dec_item *packed, uint64_t *summary,
-    const struct hufd_chunk_rec *chunk_rec, uint32_t n_chunks, struct hufd_chunk_rec *packed_rec, void *stream) {
-    const int e = pack_offsets_launch(
-        items, counts, 1u, n_items, tile_items, align, capacity, tile_sums, offsets, packed, summary, (hipStream_t)stream);
+    const struct hufd_chunk_rec *chunk_rec, uint32_t n_chunks, struct hufd_chunk_rec *packed_rec, const uint64_t *stored_rec,
+    void *stream) {
+    int e = 0;
+    if (stored_rec && n_items && tile_items) { /* (a plan with stored items: their packed lengths for their symbols) */
+        pack_batch batch{};
+        batch.second = items;
+        batch.directory = stored_rec;
+        e = pack_batch_launch(
+            counts, kPackUnstored, n_items, tile_items, tile_sums, offsets, summary, batch, (hipStream_t)stream, align, capacity, packed);
+    } else {
+        e = pack_offsets_launch(
+            items, counts, 1u, n_items, tile_items, align, capacity, tile_sums, offsets, packed, summary, (hipStream_t)stream);
+    }
     if (e || n_items == 0 || n_chunks == 0) {
         return e;
     }
     hipLaunchKernelGGL(
         unpack_records_kernel, dim3((n_chunks + kPackThreads - 1) / kPackThreads), dim3(kPackThreads), 0, (hipStream_t)stream,
         (const hufd_dec_item *)nullptr, packed, chunk_rec, packed_rec, n_chunks, pack_scan{});
+    return (int)hipGetLastError();
+}
+
+int hufk_stored_copy_encode(
+    const struct hufd_enc_item *items, uint32_t n_items, const struct hufd_enc_seg *segs, uint32_t n_segs, const uint32_t *solo,
+    uint32_t n_solo, const uint32_t *tiny, uint32_t n_tiny, const uint8_t *stored, const uint64_t *offsets, uint64_t capacity,
+    const void *input, void *output, struct hufd_enc_result *results, uint64_t *counts, void *stream) {
+    if (n_items == 0) {
+        return 0;
+    }
+    const u64 by_items = ((u64)n_items + kStoredThreads - 1) / kStoredThreads;
+    const u32 item_blocks = (u32)(by_items < kStoredItemBlocks ? by_items : kStoredItemBlocks);
+    const u64 blocks = (u64)n_segs + ((u64)n_solo + kStoredWaves - 1) / kStoredWaves + ((u64)n_tiny + kStoredThreads - 1) / kStoredThreads +
+                       item_blocks;
+    if (blocks >> 31) {
+        return (int)hipErrorInvalidValue;
+    }
+    stored_job job{};
+    job.in = (const u8 *)input;
+    job.out = (u8 *)output;
+    job.n_items = n_items;
+    job.items = items;
+    job.segs = segs;
+    job.solo = solo;
+    job.tiny = tiny;
+    job.n_segs = n_segs;
+    job.n_solo = n_solo;
+    job.n_tiny = n_tiny;
+    job.stored = stored;
+    job.offsets = offsets;
+    job.capacity = capacity;
+    job.enc_results = results;
+    job.counts = counts;
+    job.item_blocks = item_blocks;
+    stored_launch(job, (u32)blocks, (hipStream_t)stream);
+    return (int)hipGetLastError();
+}
+
+int hufk_stored_copy_decode(
+    const uint64_t *stored_rec, const uint64_t *tile_first, uint64_t n_tiles, uint32_t n_items, const struct hufd_dec_item *placed,
+    struct hufd_dec_result *results, const void *input, void *output, void *stream) {
+    if (n_items == 0) {
+        return 0;
+    }
+    const u64 blocks = n_tiles + ((u64)n_items + kStoredWaves - 1) / kStoredWaves + ((u64)n_items + kStoredThreads - 1) / kStoredThreads;
+    if (n_tiles >> 31 || blocks >> 31) {
+        return (int)hipErrorInvalidValue;
+    }
+    stored_job job{};
+    job.in = (const u8 *)input;
+    job.out = (u8 *)output;
+    job.n_items = n_items;
+    job.receiver = 1;
+    job.rec = stored_rec;
+    job.tile_first = tile_first;
+    job.n_tiles = (u32)n_tiles;
+    job.placed = placed;
+    job.dec_results = results;
+    stored_launch(job, (u32)blocks, (hipStream_t)stream);
+    return (int)hipGetLastError();
+}
+
+int hufk_stored_records(
+    const uint64_t *offsets, const uint64_t *lengths, const uint8_t *stored, uint32_t n_items, uint64_t *stored_rec, void *stream) {
+    if (n_items == 0) {
+        return 0;
+    }
+    stored_job job{};
+    job.n_items = n_items;
+    job.receiver = 2;
+    job.offsets = offsets;
+    job.lengths = lengths;
+    job.stored = stored;
+    job.new_rec = stored_rec;
+    stored_launch(job, (n_items + kStoredThreads - 1) / kStoredThreads, (hipStream_t)stream);
     return (int)hipGetLastError();
 }
 

@@ -68,8 +68,9 @@ __device__ __forceinline__ raw_item load_item(const hufd_item_source &src, u32 i
         r.out_off = e.in_off;
         r.out_cap = e.in_len;
         r.bits = 0;
-    } else if (!ENC && src.kind == HUFD_ITEMS_PACKED_INPUT) {
-        /* item i of a packed buffer: from its offset to the next one, or as long as the sender says */
+    } else if (!ENC && (src.kind == HUFD_ITEMS_PACKED_INPUT || src.kind == HUFD_ITEMS_PACKED_STORED_INPUT)) {
+        /* item i of a packed buffer: from its offset to the next one, or as long as the sender says -- or, flagged as stored
+         * raw, nothing for the decode kernels (a flag that is neither 0 nor 1: no plan) */
         const u64 at = src.packed_offsets[i];
         r.in_off = at;
         if (src.packed_lengths) {
@@ -79,6 +80,11 @@ __device__ __forceinline__ raw_item load_item(const hufd_item_source &src, u32 i
             const u64 next = src.packed_offsets[(u64)i + 1];
             r.in_len = next >= at ? next - at : 0;
             r.bad = next < at;
+        }
+        if (src.kind == HUFD_ITEMS_PACKED_STORED_INPUT) {
+            const u32 flag = src.packed_stored[i];
+            r.in_len = flag ? 0 : r.in_len;
+            r.bad |= flag > 1u ? 1u : 0u;
         }
         r.out_off = 0;
         r.out_cap = 0;

@@ -15,6 +15,7 @@
 #include <aws/compression/huffman_amd_packed.h>
 #include <aws/compression/huffman_amd_plan_counts.h>
 #include <aws/compression/huffman_amd_ranges.h>
+#include <aws/compression/huffman_amd_stored.h>
 
 #include <assert.h>
 #include <stdlib.h>
@@ -860,7 +861,7 @@ static int enc_plan_fill(
     p->largest_out_cap = stats.largest_out_cap;
     p->most_overflow_bits = stats.worst_bits;
     p->longest_in_len = stats.longest;
-    p->packed = p->packed_sized = false;
+    p->packed = p->packed_sized = p->stored = false;
     p->block_indexed = false;
     if (n_items >= PLAN_ON_DEVICE_MIN_ITEMS && n_items < 0xFFFFFFFFull && stats.shortest >= 1 && stats.longest <= tiny_limit &&
         stats.worst_bits <= 32) {
@@ -1087,7 +1088,7 @@ static int enc_plan_fill_on_device(struct aws_huffman_amd_encode_plan *p, const 
     p->largest_out_cap = 0;
     p->most_overflow_bits = 0;
     p->longest_in_len = 0;
-    p->packed = p->packed_sized = false;
+    p->packed = p->packed_sized = p->stored = false;
     p->block_indexed = false;
     if (n_items == 0) {
         return AWS_OP_SUCCESS;
@@ -1250,6 +1251,9 @@ static int enc_plan_launch_items(
     a.fail_tile = p->engine->encode_fails;
     p->last_input = device_input;
     p->last_output = device_output;
+    if (!length_only) {
+        p->stored = false; /* (a stored launch says so behind its encode pass) */
+    }
     p->launched = !length_only; /* (a length query leaves lengths in the records and no output: nothing to chain a decode to) */
     p->last_single_pass =
         a.single_pass && (p->n_segs || p->n_solo) && !length_only && hufk_encode_one_pass_applies(&p->engine->tables);
@@ -1304,7 +1308,7 @@ static int enc_plan_reserve_packed(struct aws_huffman_amd_encode_plan *p, size_t
     size_t total = 0;
     const size_t at_items = arena_cut(&total, ci * sizeof(struct hufd_enc_item));
     const size_t at_sums = arena_cut(&total, 2 * n_tiles * sizeof(uint64_t));
-    const size_t at_summary = arena_cut(&total, 2 * sizeof(uint64_t));
+    const size_t at_summary = arena_cut(&total, 4 * sizeof(uint64_t)); /* (the last two: a stored launch's counts) */
     p->d_packed_arena = hufs_malloc(total);
     if (!p->d_packed_arena) {
         return 2;
@@ -1332,7 +1336,7 @@ static int enc_plan_launch_packed_empty(struct aws_huffman_amd_encode_plan *p, u
     if (e) {
         return raise_hip(e);
     }
-    p->packed = false;
+    p->packed = p->stored = false;
     p->packed_sized = true;
     return AWS_OP_SUCCESS;
 }
@@ -1393,6 +1397,100 @@ int aws_huffman_amd_encode_plan_launch_packed(
         }
     }
     return enc_plan_launch_packed_items(p, device_input, device_output, stream);
+}
+
+/* ------------------------------------------------------------------ items stored raw, the sender (huffman_amd_stored.h) */
+
+int aws_huffman_amd_encode_plan_launch_packed_stored(
+    struct aws_huffman_amd_encode_plan *p,
+    const void *device_input,
+    void *device_output,
+    uint64_t output_capacity,
+    uint64_t *device_offsets,
+    uint8_t *device_stored,
+    uint32_t align,
+    void *stream) {
+
+    if (!packed_launch_args_ok(p, device_output, output_capacity, device_offsets, align) || !device_stored) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    if (engine_never_fitted(p->engine)) {
+        return aws_raise_error(AWS_ERROR_INVALID_STATE);
+    }
+    void *st = stream ? stream : p->engine->stream;
+    if (p->n_items == 0) {
+        if (enc_plan_launch_packed_empty(p, device_offsets, st)) {
+            return AWS_OP_ERR;
+        }
+        p->stored = true;
+        return AWS_OP_SUCCESS;
+    }
+    uint32_t tile_items = 0;
+    if (enc_plan_packed_tile_items(p, &tile_items)) {
+        return AWS_OP_ERR;
+    }
+    /* a packed launch's three stages with the scan that decides -- lengths, flags, offsets, no room for a stored item in the
+     * second record array --, then the copy of the stored items and their records behind the encode pass: one stream */
+    if (enc_plan_launch_items(p, p->d_items, device_input, device_output, true, stream, NULL)) {
+        return AWS_OP_ERR;
+    }
+    {
+        ON_DEVICE(p->engine->device);
+        const int e = hufk_pack_offsets_stored(
+            p->d_items, p->d_results, p->n_items, tile_items, align, output_capacity, p->d_pack_tile_sums, device_offsets,
+            p->d_packed_items, p->d_pack_summary, device_stored, st);
+        if (e) {
+            return raise_hip(e);
+        }
+    }
+    if (enc_plan_launch_packed_items(p, device_input, device_output, stream)) {
+        return AWS_OP_ERR;
+    }
+    {
+        ON_DEVICE(p->engine->device);
+        int e = hufk_stored_copy_encode(
+            p->d_items, p->n_items, p->d_segs, p->n_segs, p->d_solo, p->n_solo, p->d_tiny, p->n_tiny, device_stored, device_offsets,
+            output_capacity, device_input, device_output, p->d_results, p->d_pack_summary + 2, st);
+        if (!e) {
+            e = plan_mark_done(&p->done_event, &p->done_on_engine_stream, p->engine, stream);
+        }
+        if (e) {
+            /* (raw items were not placed: neither the records, nor the layout, nor the sizes are what a fetch, a chained plan or
+             * a size query should read) */
+            p->launched = p->packed = p->packed_sized = false;
+            return raise_hip(e);
+        }
+    }
+    p->stored = true;
+    return AWS_OP_SUCCESS;
+}
+
+int aws_huffman_amd_encode_plan_stored_size(
+    struct aws_huffman_amd_encode_plan *p,
+    uint64_t *stored_items,
+    uint64_t *stored_bytes,
+    void *stream) {
+
+    if (!p || !p->packed_sized || !p->stored) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    uint64_t counts[2] = {0, 0};
+    ON_DEVICE(p->engine->device);
+    void *st = stream ? stream : p->engine->stream;
+    int err = p->n_items ? hufs_copy_d2h(counts, p->d_pack_summary + 2, sizeof(counts), st) : 0;
+    if (!err) {
+        err = hufs_stream_sync(st);
+    }
+    if (err) {
+        return raise_hip(err);
+    }
+    if (stored_items) {
+        *stored_items = counts[0];
+    }
+    if (stored_bytes) {
+        *stored_bytes = counts[1];
+    }
+    return AWS_OP_SUCCESS;
 }
 
 int aws_huffman_amd_encode_plan_packed_size(
@@ -1699,7 +1797,7 @@ static int dec_plan_fill(
     p->n_items = p->n_chunks = p->n_large = p->n_runs = p->n_tail = p->n_fixed = p->n_wide = 0;
     p->quiet = false; /* (other items: nothing is known of what their launches list) */
     p->launches_with_chunks = 0; /* (... and no launch of these has left a summary to read it from) */
-    p->packed = p->packed_sized = false;
+    p->packed = p->packed_sized = p->stored = false;
     p->longest_in_len = 0;
     p->n_tiny = p->n_deep = 0;
     memset(&p->stats, 0, sizeof(p->stats));
@@ -2053,11 +2151,16 @@ static int dec_items_to_host(
         if (!e) {
             e = hufs_stream_sync(st);
         }
-    } else if (src->kind == HUFD_ITEMS_PACKED_INPUT) {
+    } else if (src->kind == HUFD_ITEMS_PACKED_INPUT || src->kind == HUFD_ITEMS_PACKED_STORED_INPUT) {
         const size_t n_offsets = src->packed_lengths ? n_items : n_items + 1;
+        const bool flagged = src->kind == HUFD_ITEMS_PACKED_STORED_INPUT;
         uint64_t *at = malloc((n_offsets ? n_offsets : 1) * sizeof(*at));
         uint64_t *len = malloc((n_items ? n_items : 1) * sizeof(*len));
-        e = at && len ? 0 : 2;
+        uint8_t *flag = calloc(n_items ? n_items : 1, 1);
+        e = at && len && flag ? 0 : 2;
+        if (!e && n_items && flagged) {
+            e = hufs_copy_d2h(flag, src->packed_stored, n_items, st);
+        }
         if (!e && n_items) {
             e = hufs_copy_d2h(at, src->packed_offsets, n_offsets * sizeof(*at), st);
         }
@@ -2069,12 +2172,14 @@ static int dec_items_to_host(
         }
         for (size_t i = 0; i < n_items && !e; ++i) {
             /* (offsets that decrease: a length no plan takes, as the device planner's `invalid`) */
-            const bool bad = src->packed_lengths ? (i > 0 && at[i - 1] > at[i]) : at[i + 1] < at[i];
+            const bool bad = (src->packed_lengths ? (i > 0 && at[i - 1] > at[i]) : at[i + 1] < at[i]) || flag[i] > 1;
             items[i].in_offset = at[i];
-            items[i].in_len = bad ? UINT64_MAX : (src->packed_lengths ? len[i] : at[i + 1] - at[i]);
+            /* (an item stored raw: nothing for the decode kernels) */
+            items[i].in_len = bad ? UINT64_MAX : (flag[i] ? 0 : (src->packed_lengths ? len[i] : at[i + 1] - at[i]));
         }
         free(at);
         free(len);
+        free(flag);
     } else if (src->kind == HUFD_ITEMS_BLOCK_RANGES) {
         /* (the index whole: 8 bytes a block; load_item of plan_kernels.hip is the rule this loop restates) */
         struct hufd_block_range *ranges = malloc((n_items ? n_items : 1) * sizeof(*ranges));
@@ -2302,7 +2407,7 @@ static int dec_plan_fill_on_device(struct aws_huffman_amd_decode_plan *p, const 
     p->n_items = p->n_chunks = p->n_large = p->n_runs = p->n_tail = p->n_fixed = p->n_wide = 0;
     p->quiet = false; /* (other items: nothing is known of what their launches list) */
     p->launches_with_chunks = 0; /* (... and no launch of these has left a summary to read it from) */
-    p->packed = p->packed_sized = false;
+    p->packed = p->packed_sized = p->stored = false;
     p->longest_in_len = 0;
     p->n_tiny = p->n_deep = 0;
     memset(&p->stats, 0, sizeof(p->stats));
@@ -2417,6 +2522,7 @@ void aws_huffman_amd_decode_plan_destroy(struct aws_huffman_amd_decode_plan *p) 
         hufs_free(p->d_wide_block);
         hufs_free(p->d_fixed);
         hufs_free(p->d_range_bits);
+        hufs_free(p->d_stored_arena);
         free(p->h_wide);
         free(p->h_items);
         free(p);
@@ -2512,7 +2618,7 @@ int aws_huffman_amd_decode_plan_launch_staged(
     void *stream,
     void **stage_events) {
 
-    if (engine_never_fitted(p->engine)) {
+    if (engine_never_fitted(p->engine) || p->stored) { /* (stored items have no place of their own: such a plan is for packed launches) */
         return aws_raise_error(AWS_ERROR_INVALID_STATE);
     }
     struct hufk_decode_args a;
@@ -2611,6 +2717,11 @@ int aws_huffman_amd_decode_plan_launch_packed(
     pk.summary = p->d_pack_summary;
     pk.items = p->d_packed_items;
     pk.chunk_rec = p->d_packed_chunk_rec;
+    if (p->stored) {
+        pk.stored_rec = p->d_stored_rec;
+        pk.stored_tile_first = p->d_stored_tile_first;
+        pk.stored_tiles = p->stored_tiles;
+    }
     struct hufk_decode_args a;
     dec_plan_launch_args(p, &a, device_input, device_output, NULL);
     err = hufk_decode_launch_packed(&a, &pk, st);
@@ -2677,6 +2788,97 @@ int aws_huffman_amd_decode_plan_reset_packed_input(
     src.packed_offsets = device_offsets;
     src.packed_lengths = device_lengths;
     return dec_plan_fill_on_device(p, &src, item_count, stream);
+}
+
+/* ------------------------------------------------------------------ items stored raw, the receiver (huffman_amd_stored.h) */
+
+/* the plan's stored records, the tiles in front of each item and the tile sums of their scan (grown, never shrunk) */
+static int dec_plan_reserve_stored(struct aws_huffman_amd_decode_plan *p, size_t n_items, size_t n_tiles) {
+    if (p->d_stored_arena && n_items <= p->cap_stored_items && n_tiles <= p->cap_stored_tiles) {
+        return 0;
+    }
+    hufs_free(p->d_stored_arena); /* (waits for what still reads it) */
+    p->d_stored_arena = NULL;
+    p->cap_stored_items = p->cap_stored_tiles = 0;
+    size_t total = 0;
+    const size_t at_rec = arena_cut(&total, 2 * n_items * sizeof(uint64_t));
+    const size_t at_first = arena_cut(&total, (n_items + 1) * sizeof(uint64_t));
+    const size_t at_sums = arena_cut(&total, 2 * n_tiles * sizeof(uint64_t));
+    p->d_stored_arena = hufs_malloc(total);
+    if (!p->d_stored_arena) {
+        return 2;
+    }
+    p->d_stored_rec = (void *)((uint8_t *)p->d_stored_arena + at_rec);
+    p->d_stored_tile_first = (void *)((uint8_t *)p->d_stored_arena + at_first);
+    p->d_stored_tile_sums = (void *)((uint8_t *)p->d_stored_arena + at_sums);
+    p->cap_stored_items = n_items;
+    p->cap_stored_tiles = n_tiles;
+    return 0;
+}
+
+int aws_huffman_amd_decode_plan_reset_packed_stored_input(
+    struct aws_huffman_amd_decode_plan *p,
+    const uint64_t *device_offsets,
+    const uint64_t *device_lengths,
+    const uint8_t *device_stored,
+    size_t item_count,
+    void *stream) {
+
+    if (!device_stored) {
+        return aws_huffman_amd_decode_plan_reset_packed_input(p, device_offsets, device_lengths, item_count, stream);
+    }
+    if (!p) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    if ((!device_offsets && item_count) || ((uintptr_t)device_offsets & 7u) || ((uintptr_t)device_lengths & 7u)) {
+        p->quiet = false; /* (as a refused aws_huffman_amd_decode_plan_reset_packed_input) */
+        p->launches_with_chunks = 0;
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    struct hufd_item_source src;
+    memset(&src, 0, sizeof(src));
+    src.kind = HUFD_ITEMS_PACKED_STORED_INPUT;
+    src.packed_offsets = device_offsets;
+    src.packed_lengths = device_lengths;
+    src.packed_stored = device_stored;
+    /* the planner's pass checks every offset, length and flag; a stored item comes out of it without encoded bytes */
+    if (dec_plan_fill_on_device(p, &src, item_count, stream)) {
+        return AWS_OP_ERR;
+    }
+    if (p->n_items == 0) {
+        return AWS_OP_SUCCESS;
+    }
+    /* what the launches need of the three arrays: {source offset, length} of every stored item, and the tiles the copy cuts
+     * the long ones into, scanned; their number comes back (the reset has waited for the planner's totals already) */
+    void *st = stream ? stream : p->engine->stream;
+    const uint32_t tile_items = hufk_pack_tile_items(p->n_items, __atomic_load_n(&s_pack_tile_items, __ATOMIC_RELAXED));
+    uint64_t tiles = 0;
+    ON_DEVICE(p->engine->device);
+    int e = dec_plan_reserve_stored(p, p->n_items, hufk_pack_tiles(p->n_items, tile_items));
+    if (!e) {
+        e = hufk_stored_records(device_offsets, device_lengths, device_stored, p->n_items, p->d_stored_rec, st);
+    }
+    if (!e) {
+        e = hufk_stored_tiles(
+            p->d_stored_rec, p->n_items, tile_items, HUFK_STORED_TILE_BYTES, HUFK_STORED_WAVE_BYTES, p->d_stored_tile_sums,
+            p->d_stored_tile_first, st);
+    }
+    if (!e) {
+        e = hufs_copy_d2h(&tiles, p->d_stored_tile_first + p->n_items, sizeof(tiles), st);
+    }
+    if (!e) {
+        e = hufs_stream_sync(st);
+    }
+    if (e || tiles >= 0x7FFFFFFFull) {
+        p->n_items = p->n_chunks = p->n_large = p->n_runs = p->n_tail = p->n_tiny = p->n_deep = p->n_fixed = p->n_wide = 0; /* (no plan) */
+        p->n_tail_narrow = 0;
+        p->packed = p->packed_sized = false;
+        memset(&p->stats, 0, sizeof(p->stats));
+        return e ? raise_hip(e) : aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    p->stored_tiles = tiles;
+    p->stored = true;
+    return AWS_OP_SUCCESS;
 }
 
 /* ------------------------------------------------------------------ block index and range plans (huffman_amd_index.h) */
@@ -3470,6 +3672,12 @@ int aws_huffman_amd_decode_plan_from_encode(
         p->launches_with_chunks = 0;
         return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT); /* (a plan that was never launched has no records to read lengths from) */
     }
+    if (encoded->stored) {
+        /* (a stored launch left raw bytes among the codes: aws_huffman_amd_decode_plan_reset_packed_stored_input is the way back) */
+        p->quiet = false;
+        p->launches_with_chunks = 0;
+        return aws_raise_error(AWS_ERROR_INVALID_STATE);
+    }
     /* Whatever the launch produced, every item must be ONE THREAD's work for the decoder (then the plan has no chunk
      * geometry, which only the host can lay out): the most bytes an item can have left is its output capacity.  The same
      * rule as for a plan from host records (dec_tiny_limit), with the capacities for the lengths. */
@@ -3500,7 +3708,7 @@ int aws_huffman_amd_decode_plan_from_encode(
     p->n_items = p->n_chunks = p->n_large = p->n_runs = p->n_tail = p->n_fixed = p->n_wide = 0;
     p->quiet = false; /* (other items: nothing is known of what their launches list) */
     p->launches_with_chunks = 0; /* (... and no launch of these has left a summary to read it from) */
-    p->packed = p->packed_sized = false;
+    p->packed = p->packed_sized = p->stored = false;
     p->longest_in_len = 0;
     p->n_tiny = p->n_deep = 0;
     memset(&p->stats, 0, sizeof(p->stats));

@@ -114,10 +114,12 @@ struct aws_huffman_amd_encode_plan {
     void *d_packed_arena;
     struct hufd_enc_item *d_packed_items; /* [cap_packed_items] */
     uint64_t *d_pack_tile_sums;           /* [2 * cap_pack_tiles] */
-    uint64_t *d_pack_summary;             /* [2]: the total, the largest reserved length */
+    uint64_t *d_pack_summary;             /* [4]: the total, the largest reserved length; of a stored launch: the stored items, their bytes */
     size_t cap_packed_items, cap_pack_tiles;
     bool packed;       /* the last encode launch was a packed one: its output lies where d_packed_items say */
     bool packed_sized; /* ... and one was made since the plan was filled: d_pack_summary is of these items */
+    bool stored;       /* the last encode launch was aws_huffman_amd_encode_plan_launch_packed_stored (huffman_amd_stored.h): raw
+                        * items lie among the coded ones, and d_pack_summary[2], [3] count them */
     /* aws_huffman_amd_encode_plan_block_index (huffman_amd_batch_index.h): the tiles of its hot pass in front of each item,
      * the tile sums of its two scans over the items and the word that holds all blocks; ONE allocation, made by the plan's
      * first such call and grown by a later one of more items or tiles */
@@ -198,6 +200,16 @@ struct aws_huffman_amd_decode_plan {
                               * items' own capacities do not */
     bool packed;       /* the last launch was a packed one: its results are results for the room d_packed_items say */
     bool packed_sized; /* ... and one was made since the plan was filled: d_pack_summary is of these items */
+    /* a plan reset with a sender's flags (aws_huffman_amd_decode_plan_reset_packed_stored_input, huffman_amd_stored.h): the
+     * items stored raw have no encoded bytes in d_items; ONE allocation holds {source offset, length or HUFK_NOT_STORED} of
+     * every item, the tiles of the copy in front of each item and the tile sums of their scan */
+    bool stored;
+    void *d_stored_arena;
+    uint64_t *d_stored_rec;        /* [cap_stored_items][2] */
+    uint64_t *d_stored_tile_first; /* [cap_stored_items + 1] */
+    uint64_t *d_stored_tile_sums;  /* [2 * cap_stored_tiles] */
+    size_t cap_stored_items, cap_stored_tiles;
+    uint64_t stored_tiles;
 };
 
 /* the engine cache of huffman.c: what an engine is recognised by besides the coder's address, and the two ways out of it */
