@@ -605,6 +605,14 @@ static int decode_launch_stages(const struct hufk_decode_args *a, const struct h
             return e;
         }
     }
+    if (!pk && a->stored_rec) {
+        /* ranges of items stored raw, a plain launch: copied to where their ranges say, behind every kernel that writes records */
+        const int e = hufk_stored_copy_decode(
+            a->stored_rec, a->stored_tile_first, a->stored_tiles, a->n_items, a->items, a->results, a->d_in, a->d_out, st);
+        if (e) {
+            return e;
+        }
+    }
     stage_mark(a->stage_events, 3, st);
     return (int)hipGetLastError();
 }

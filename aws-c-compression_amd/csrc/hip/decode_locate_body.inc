@@ -121,6 +121,15 @@ __device__ __forceinline__ locate_position locate_item_position_of(const hufd_lo
         bytes > loc.encoded_length - at) {
         return p;
     }
+    if (loc.stored) { /* (the same in every thread of the launch) */
+        /* an item stored raw: a byte a symbol, a closed form like the one for coders of one code length -- no index entry and
+         * no encoded byte is read; its packed length must be its symbols, and a flag that is neither 0 nor 1 is not found */
+        const u32 flag = loc.stored[item];
+        if (flag) {
+            p.bit = flag == 1u && bytes == symbols ? 8 * (at + s) : HUFD_NO_BIT;
+            return p;
+        }
+    }
     const u64 base = loc.index[first];
     const u64 b = s / loc.block_symbols;
     const u32 k = (u32)(s - b * loc.block_symbols);

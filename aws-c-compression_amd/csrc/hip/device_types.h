@@ -314,7 +314,11 @@ struct hufd_item_source {
     const struct hufd_item_symbol_range *item_symbol_ranges;
     /* a packed input with items stored raw (decode, huffman_amd_stored.h): packed_offsets / packed_lengths as above, and
      * packed_stored[i] = 1 for an item whose bytes are its symbols -- no encoded bytes for the decode kernels: the plan copies
-     * it (stored_copy.hpp) -- or 0; any other byte: no plan */
+     * it (stored_copy.hpp) -- or 0; any other byte: no plan.
+     * With the two kinds of ranges by item (huffman_amd_stored_index.h; NULL: no item is stored): the flags of the batch's
+     * items, read for the items the ranges name only.  A range in an item flagged 1 -- whose packed length must be its symbols
+     * -- is its bytes as they lie: in_off = where they start, in_len = 0 (nothing for the decode kernels), out_cap = their
+     * number; the index entries of such an item are not read.  A named item's flag above 1: no plan */
     const uint8_t *packed_stored;
 };
 
@@ -360,6 +364,10 @@ struct hufd_locate {
     const uint64_t *items;
     const uint64_t *offsets;
     const uint64_t *lengths;
+    /* ... and, of a batch with items stored raw (huffman_amd_stored_index.h; NULL: none is), the items' flags: symbol s of an
+     * item flagged 1, whose packed length must be its symbols, starts at bit 8 * (offsets[item] + s) -- no index entry is read,
+     * no walk made; a flag above 1 is not found */
+    const uint8_t *stored;
 };
 
 #endif /* HUFFMAN_AMD_DEVICE_TYPES_H */

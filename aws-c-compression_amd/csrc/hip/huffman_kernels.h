@@ -133,6 +133,11 @@ struct hufk_decode_args {
     uint32_t tails_apart;           /* 1: ... and kernels of their own even where they are few among many chunks inside streams (tests:
                                      * such a launch folds them into the big kernels' grids) */
     void **stage_events; /* NULL, or 4 hipEvent_t: before sync, after sync, after scan, after emit */
+    /* a plan of ranges that holds ranges of items stored raw (huffman_amd_stored_index.h; NULL: none), for a PLAIN launch: their
+     * records and the tiles of the long ones, as hufk_decode_pack has them; `items` say where each goes */
+    const uint64_t *stored_rec;        /* [n_items][2] */
+    const uint64_t *stored_tile_first; /* [n_items + 1] */
+    uint64_t stored_tiles;
 };
 
 /* one-time per-process kernel attribute setup (dynamic LDS above 64 KiB) */
@@ -281,6 +286,11 @@ int hufk_stored_copy_encode(
     const void *input, void *output, struct hufd_enc_result *results, uint64_t *counts, void *stream);
 int hufk_stored_records(
     const uint64_t *offsets, const uint64_t *lengths, const uint8_t *stored, uint32_t n_items, uint64_t *stored_rec, void *stream);
+/* ... of a plan of ranges of an indexed batch (huffman_amd_stored_index.h): stored_rec[r] = {items[r].in_off, items[r].out_cap}
+ * for a range of bytes in an item flagged 1, {.., HUFK_NOT_STORED} for any other; ranges: four words each, the first the item */
+int hufk_stored_range_records(
+    const uint64_t *ranges, const uint8_t *stored, const struct hufd_dec_item *items, uint32_t n_items, uint64_t *stored_rec,
+    void *stream);
 int hufk_stored_tiles(
     const uint64_t *stored_rec, uint32_t n_items, uint32_t tile_items, uint64_t tile_bytes, uint64_t wave_bytes, uint64_t *tile_sums,
     uint64_t *tile_first, void *stream);
@@ -367,6 +377,12 @@ int hufk_pack_offsets_indexed(
     const struct hufd_enc_item *items, uint32_t n_items, uint32_t tile_items, uint64_t align, uint64_t capacity,
     const uint64_t *directory, const uint64_t *index, uint64_t index_capacity, uint64_t *tile_sums, uint64_t *offsets,
     struct hufd_enc_item *packed, uint64_t *summary, void *stream);
+/* The two together (huffman_amd_stored_index.h): hufk_pack_offsets_stored with the coded length hufk_pack_offsets_indexed
+ * reads out of the scanned index.  An index that does not fit: every length 0, so also every flag. */
+int hufk_pack_offsets_stored_indexed(
+    const struct hufd_enc_item *items, uint32_t n_items, uint32_t tile_items, uint64_t align, uint64_t capacity,
+    const uint64_t *directory, const uint64_t *index, uint64_t index_capacity, uint64_t *tile_sums, uint64_t *offsets,
+    struct hufd_enc_item *packed, uint64_t *summary, uint8_t *stored, void *stream);
 
 /* Where symbols of an indexed stream start (decode_locate_body.inc, huffman_amd_ranges.h): job->bits[i] for the positions
  * [0, job->count) of `job` (its `first` and `coop` are the launches' own), under the decode tables of `tables`.  One launch

@@ -131,6 +131,11 @@ constexpr u64 kPackMaxBlocks = 1ull << 32; /* what an item counts at most: no su
 constexpr u32 kPackStored = 6;
 constexpr u32 kPackUnstored = 7;
 constexpr u32 kPackStoredTiles = 8;
+/* A tenth, the offsets of aws_huffman_amd_encode_plan_launch_packed_stored_indexed (huffman_amd_stored_index.h): kPackStored
+ * with the coded length kPackIndexed reads out of the scanned index in place of the length pass's record -- builds of the
+ * bodies with both constants, INDEXED and STORED == kPackStored.  `lengths` and batch.second are both the plan's item records.
+ * Where the index does not fit every coded length is 0, so no item is stored and every flag is 0. */
+constexpr u32 kPackStoredIndexed = 9;
 constexpr u64 kPackNotStored = HUFK_NOT_STORED;
 
 struct pack_batch {
@@ -155,11 +160,27 @@ __device__ __forceinline__ bool pack_batch_fits(u64 blocks, u64 capacity) {
     return blocks < capacity && blocks < kPackMaxBlocks;
 }
 
+/* what the scanned index says of item i's code, with its carried bits, in bytes (0 where the index does not fit) */
+__device__ __forceinline__ u64 pack_indexed_length(const hufd_enc_item *item, u64 i, const pack_batch &batch) {
+    if (!pack_batch_fits(*batch.count, batch.capacity)) { /* (the same in every thread of the launch) */
+        return 0;
+    }
+    const u64 from = batch.index[batch.directory[2 * i]], to = batch.index[batch.directory[2 * i + 2]];
+    return (to - from + item->ovf_bits + 7) / 8;
+}
+
+/* the coded length of item i of a sender's batch: the length pass's record, or (INDEXED) the scanned index */
+template <bool INDEXED>
+__device__ __forceinline__ u64 pack_coded_length(const void *lengths, const hufd_enc_item *item, u64 i, const pack_batch &batch) {
+    return INDEXED ? pack_indexed_length(item, i, batch)
+                   : pack_encode::length(reinterpret_cast<const pack_encode::measured *>(lengths), i);
+}
+
 template <bool BATCH, bool INDEXED = false, u32 STORED = 0>
 __device__ __forceinline__ u64 pack_length(const void *lengths, u32 decode, u64 i, const pack_batch &batch) {
     if (STORED == kPackStored) {
         const hufd_enc_item *item = reinterpret_cast<const hufd_enc_item *>(batch.second) + i;
-        const u64 coded = pack_encode::length(reinterpret_cast<const pack_encode::measured *>(lengths), i);
+        const u64 coded = pack_coded_length<INDEXED>(lengths, item, i, batch);
         return pack_item_stored(item, coded) ? item->in_len : coded;
     }
     if (STORED == kPackUnstored) {
@@ -174,11 +195,7 @@ __device__ __forceinline__ u64 pack_length(const void *lengths, u32 decode, u64 
         return len == kPackNotStored || len < batch.wave_bytes ? 0 : (len + batch.tile_blocks - 1) / batch.tile_blocks;
     }
     if (INDEXED) {
-        if (!pack_batch_fits(*batch.count, batch.capacity)) { /* (the same in every thread of the launch) */
-            return 0;
-        }
-        const u64 from = batch.index[batch.directory[2 * i]], to = batch.index[batch.directory[2 * i + 2]];
-        return (to - from + reinterpret_cast<const hufd_enc_item *>(lengths)[i].ovf_bits + 7) / 8;
+        return pack_indexed_length(reinterpret_cast<const hufd_enc_item *>(lengths) + i, i, batch);
     }
     if (BATCH && decode >= kPackBlocks) {
         const u64 block_symbols = batch.block_symbols, tile_blocks = batch.tile_blocks, wave_bytes = batch.wave_bytes;
@@ -324,8 +341,7 @@ __device__ __forceinline__ void pack_offsets_body(
             if (STORED == kPackStored) {
                 const pack_encode::item *from = reinterpret_cast<const pack_encode::item *>(batch.second) + i;
                 pack_encode::item *to = reinterpret_cast<pack_encode::item *>(packed) + i;
-                const bool stored =
-                    pack_item_stored(from, pack_encode::length(reinterpret_cast<const pack_encode::measured *>(lengths), i));
+                const bool stored = pack_item_stored(from, pack_coded_length<INDEXED>(lengths, from, i, batch));
                 pack_encode::place(from, to, off, 0, reserved, capacity);
                 if (stored) {
                     to->out_cap = 0;
@@ -446,6 +462,9 @@ __global__ __launch_bounds__(kPackThreads) void unpack_records_kernel(
         } else if (scan.decode == kPackStored) {
             pack_tile_sums_body<true, false, kPackStored>(
                 scan.lengths, kPackStored, scan.n_items, scan.tile_items, scan.align_mask, scan.tile_sums, scan.batch);
+        } else if (scan.decode == kPackStoredIndexed) {
+            pack_tile_sums_body<true, true, kPackStored>(
+                scan.lengths, kPackStoredIndexed, scan.n_items, scan.tile_items, scan.align_mask, scan.tile_sums, scan.batch);
         } else if (scan.decode == kPackUnstored) {
             pack_tile_sums_body<true, false, kPackUnstored>(
                 scan.lengths, kPackUnstored, scan.n_items, scan.tile_items, scan.align_mask, scan.tile_sums, scan.batch);
@@ -462,6 +481,10 @@ __global__ __launch_bounds__(kPackThreads) void unpack_records_kernel(
         } else if (scan.decode == kPackStored) {
             pack_offsets_body<true, false, kPackStored>(
                 scan.batch.second, scan.lengths, kPackStored, scan.n_items, scan.tile_items, scan.align_mask, scan.out_capacity,
+                scan.tile_sums, scan.offsets, scan.packed, scan.summary, scan.batch);
+        } else if (scan.decode == kPackStoredIndexed) {
+            pack_offsets_body<true, true, kPackStored>(
+                scan.batch.second, scan.lengths, kPackStoredIndexed, scan.n_items, scan.tile_items, scan.align_mask, scan.out_capacity,
                 scan.tile_sums, scan.offsets, scan.packed, scan.summary, scan.batch);
         } else if (scan.decode == kPackUnstored) {
             pack_offsets_body<true, false, kPackUnstored>(
@@ -642,6 +665,24 @@ int hufk_pack_offsets_stored(
         lengths, kPackStored, n_items, tile_items, tile_sums, offsets, summary, batch, (hipStream_t)stream, align, capacity, packed);
 }
 
+int hufk_pack_offsets_stored_indexed(
+    const struct hufd_enc_item *items, uint32_t n_items, uint32_t tile_items, uint64_t align, uint64_t capacity,
+    const uint64_t *directory, const uint64_t *index, uint64_t index_capacity, uint64_t *tile_sums, uint64_t *offsets,
+    struct hufd_enc_item *packed, uint64_t *summary, uint8_t *stored, void *stream) {
+    if (n_items == 0 || tile_items == 0) {
+        return 0;
+    }
+    pack_batch batch{};
+    batch.capacity = index_capacity;
+    batch.index = const_cast<uint64_t *>(index); /* (read only by this kind) */
+    batch.count = directory + 2 * (uint64_t)n_items;
+    batch.directory = directory;
+    batch.second = items;
+    batch.stored = stored;
+    return pack_batch_launch(
+        items, kPackStoredIndexed, n_items, tile_items, tile_sums, offsets, summary, batch, (hipStream_t)stream, align, capacity, packed);
+}
+
 int hufk_stored_tiles(
     const uint64_t *stored_rec, uint32_t n_items, uint32_t tile_items, uint64_t tile_bytes, uint64_t wave_bytes, uint64_t *tile_sums,
     uint64_t *tile_first, void *stream) {
@@ -760,6 +801,23 @@ int hufk_stored_records(
     job.offsets = offsets;
     job.lengths = lengths;
     job.stored = stored;
+    job.new_rec = stored_rec;
+    stored_launch(job, (n_items + kStoredThreads - 1) / kStoredThreads, (hipStream_t)stream);
+    return (int)hipGetLastError();
+}
+
+int hufk_stored_range_records(
+    const uint64_t *ranges, const uint8_t *stored, const struct hufd_dec_item *items, uint32_t n_items, uint64_t *stored_rec,
+    void *stream) {
+    if (n_items == 0) {
+        return 0;
+    }
+    stored_job job{};
+    job.n_items = n_items;
+    job.receiver = 3;
+    job.offsets = ranges;
+    job.stored = stored;
+    job.placed = items;
     job.new_rec = stored_rec;
     stored_launch(job, (n_items + kStoredThreads - 1) / kStoredThreads, (hipStream_t)stream);
     return (int)hipGetLastError();

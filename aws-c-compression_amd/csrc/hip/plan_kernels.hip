@@ -158,6 +158,7 @@ __device__ __forceinline__ raw_item load_item(const hufd_item_source &src, u32 i
             const u64 next = src.batch_directory[2 * g.item + 2];
             const u64 blocks = symbols / src.block_symbols + (symbols % src.block_symbols ? 1u : 0u);
             const u64 at = src.packed_offsets[g.item];
+            const u32 flag = src.packed_stored ? src.packed_stored[g.item] : 0u; /* (above 1: no item) */
             u64 bytes = 0;
             bool placed = true;
             if (src.packed_lengths) {
@@ -167,8 +168,22 @@ __device__ __forceinline__ raw_item load_item(const hufd_item_source &src, u32 i
                 placed = behind >= at;
                 bytes = behind - at;
             }
-            if (next >= first && next < src.index_entries && next - first == blocks && g.first_block <= blocks &&
-                g.block_count <= blocks - g.first_block && placed && at <= src.encoded_length && bytes <= src.encoded_length - at) {
+            const bool framed = next >= first && next < src.index_entries && next - first == blocks && g.first_block <= blocks &&
+                                g.block_count <= blocks - g.first_block && placed && at <= src.encoded_length &&
+                                bytes <= src.encoded_length - at;
+            if (flag == 1u) {
+                /* an item stored raw: its bytes are its symbols, block b the bytes from b * block_symbols on.  The index
+                 * entries of its blocks say what its code would have been: they are not read */
+                if (framed && bytes == symbols) {
+                    r.bad = 0;
+                    if (g.block_count) {
+                        const u64 lo = g.first_block * src.block_symbols; /* (at most symbols: no product below overflows) */
+                        const u64 hi = g.first_block + g.block_count == blocks ? symbols : lo + g.block_count * src.block_symbols;
+                        r.in_off = src.encoded_offset + at + lo;
+                        r.out_cap = hi - lo;
+                    }
+                }
+            } else if (flag == 0u && framed) {
                 const u64 base = src.block_index[first];
                 const u64 x0 = src.block_index[first + g.first_block], x1 = src.block_index[first + g.first_block + g.block_count];
                 const u64 from = x0 - base, to = x1 - base;
@@ -211,13 +226,17 @@ __device__ __forceinline__ raw_item load_item(const hufd_item_source &src, u32 i
             }
             const u64 from = src.located_bits[2 * (u64)i], to = src.located_bits[2 * (u64)i + 1];
             const u64 first_byte = from / 8, end_byte = to / 8 + (to % 8 ? 1 : 0);
+            /* (an item stored raw: the locate body's closed form left the ends, a byte a symbol; the range is its bytes as
+             * they lie, nothing for the decode kernels) */
+            const u32 flag = src.packed_stored ? src.packed_stored[g.item] : 0u;
+            const bool raw_ok = flag == 0u || (flag == 1u && bytes == symbols && from % 8 == 0 && to - from == 8 * g.symbol_count);
             if (g.first_symbol <= symbols && g.symbol_count <= symbols - g.first_symbol && placed && at <= src.encoded_length &&
                 bytes <= src.encoded_length - at && from != HUFD_NO_BIT && to != HUFD_NO_BIT && to >= from && first_byte >= at &&
-                end_byte <= at + bytes) {
+                end_byte <= at + bytes && raw_ok) {
                 r.bad = 0;
                 if (g.symbol_count) { /* (none: an empty item) */
                     r.in_off = src.encoded_offset + first_byte;
-                    r.in_len = end_byte - first_byte; /* (4 GiB or more: refused with every such item) */
+                    r.in_len = flag ? 0 : end_byte - first_byte; /* (4 GiB or more: refused with every such item) */
                     r.bits = (u32)(from % 8);
                     r.out_cap = g.symbol_count;
                 }

@@ -16,6 +16,11 @@
  * workgroup a tile, found by a search over the scanned tiles, a wave an item shorter than a tile's quarter; and rewrites
  * their result records.
  *
+ * Ranges of an indexed batch with stored items (huffman_amd_stored_index.h): the plan of such a reset holds a range in a stored
+ * item as {in_off = where its bytes start, in_len = 0, out_off = the caller's, out_cap = their number}.  The reset makes the
+ * same records and tiles from these, a thread a range, and a PLAIN launch runs the receiver's copy behind its emit stage with
+ * the plan's own item records for the places: destinations come from the ranges, in any order, not from a scan.
+ *
  * A range is copied at any source and destination address: up to 15 bytes one by one until the destination is 16-byte
  * aligned, whole 16-byte groups -- loaded at any alignment, stored aligned, four a thread in flight --, then up to 15 bytes
  * one by one.  Nothing outside the range is read or written.  (A lone lane's range: stored_copy_lane.)
@@ -34,7 +39,7 @@ struct stored_job {
     const u8 *in;
     u8 *out;
     u32 n_items;
-    u32 receiver; /* 0: the sender's copy, 1: the receiver's, 2: the receiver's records at a reset (the same in every thread of the launch) */
+    u32 receiver; /* 0: the sender's copy, 1: the receiver's, 2: the receiver's records at a reset, 3: those of a reset to ranges (the same in every thread of the launch) */
     /* sender: the plan's records and lists, the flags and offsets the scan wrote, the caller's capacity */
     const hufd_enc_item *items;
     const hufd_enc_seg *segs;
@@ -53,7 +58,8 @@ struct stored_job {
     const hufd_dec_item *placed;
     hufd_dec_result *dec_results;
     /* the receiver's reset: the sender's lengths (NULL: up to the next offset; `offsets`, `stored`: the other two arrays) and
-     * the records to write */
+     * the records to write.  A reset to ranges: `offsets` is the ranges, four words each, the first the item; `stored` the
+     * batch's flags; `placed` the plan's item records */
     const u64 *lengths;
     u64 *new_rec;
 };
@@ -165,9 +171,26 @@ __device__ __forceinline__ void stored_records_body(const stored_job &job) {
     job.new_rec[2 * (u64)i + 1] = job.stored[i] == 1 ? (job.lengths ? job.lengths[i] : job.offsets[(u64)i + 1] - at) : HUFK_NOT_STORED;
 }
 
+/* ... and from the item records of a plan of ranges (the planner's pass in front has checked every range, its item and
+ * that item's flag): a range of no bytes is an empty item, not a stored one */
+__device__ __forceinline__ void stored_range_records_body(const stored_job &job) {
+    const u32 i = blockIdx.x * kStoredThreads + threadIdx.x;
+    if (i >= job.n_items) {
+        return;
+    }
+    const u64 item = job.offsets[4 * (u64)i];
+    const u64 len = job.placed[i].out_cap;
+    job.new_rec[2 * (u64)i] = job.placed[i].in_off;
+    job.new_rec[2 * (u64)i + 1] = job.stored[item] == 1 && len ? len : HUFK_NOT_STORED;
+}
+
 __device__ __forceinline__ void stored_copy_body(const stored_job &job) {
-    if (job.receiver == 2) { /* (the same in every thread of the launch) */
-        stored_records_body(job);
+    if (job.receiver >= 2) { /* (the same in every thread of the launch) */
+        if (job.receiver == 2) {
+            stored_records_body(job);
+        } else {
+            stored_range_records_body(job);
+        }
         return;
     }
     const u32 t = threadIdx.x, lane = t & (kWave - 1), wave = t / kWave;

@@ -16,6 +16,7 @@
 #include <aws/compression/huffman_amd_plan_counts.h>
 #include <aws/compression/huffman_amd_ranges.h>
 #include <aws/compression/huffman_amd_stored.h>
+#include <aws/compression/huffman_amd_stored_index.h>
 
 #include <assert.h>
 #include <stdlib.h>
@@ -1401,6 +1402,34 @@ int aws_huffman_amd_encode_plan_launch_packed(
 
 /* ------------------------------------------------------------------ items stored raw, the sender (huffman_amd_stored.h) */
 
+/* the tail of a stored launch, behind the encode pass over the second record array: the copy of the stored items and their
+ * records, and the plan's state */
+static int enc_plan_launch_stored_copy(
+    struct aws_huffman_amd_encode_plan *p,
+    const void *device_input,
+    void *device_output,
+    uint64_t output_capacity,
+    const uint64_t *device_offsets,
+    const uint8_t *device_stored,
+    void *stream) {
+
+    ON_DEVICE(p->engine->device);
+    int e = hufk_stored_copy_encode(
+        p->d_items, p->n_items, p->d_segs, p->n_segs, p->d_solo, p->n_solo, p->d_tiny, p->n_tiny, device_stored, device_offsets,
+        output_capacity, device_input, device_output, p->d_results, p->d_pack_summary + 2, stream ? stream : p->engine->stream);
+    if (!e) {
+        e = plan_mark_done(&p->done_event, &p->done_on_engine_stream, p->engine, stream);
+    }
+    if (e) {
+        /* (raw items were not placed: neither the records, nor the layout, nor the sizes are what a fetch, a chained plan or
+         * a size query should read) */
+        p->launched = p->packed = p->packed_sized = false;
+        return raise_hip(e);
+    }
+    p->stored = true;
+    return AWS_OP_SUCCESS;
+}
+
 int aws_huffman_amd_encode_plan_launch_packed_stored(
     struct aws_huffman_amd_encode_plan *p,
     const void *device_input,
@@ -1446,23 +1475,7 @@ int aws_huffman_amd_encode_plan_launch_packed_stored(
     if (enc_plan_launch_packed_items(p, device_input, device_output, stream)) {
         return AWS_OP_ERR;
     }
-    {
-        ON_DEVICE(p->engine->device);
-        int e = hufk_stored_copy_encode(
-            p->d_items, p->n_items, p->d_segs, p->n_segs, p->d_solo, p->n_solo, p->d_tiny, p->n_tiny, device_stored, device_offsets,
-            output_capacity, device_input, device_output, p->d_results, p->d_pack_summary + 2, st);
-        if (!e) {
-            e = plan_mark_done(&p->done_event, &p->done_on_engine_stream, p->engine, stream);
-        }
-        if (e) {
-            /* (raw items were not placed: neither the records, nor the layout, nor the sizes are what a fetch, a chained plan or
-             * a size query should read) */
-            p->launched = p->packed = p->packed_sized = false;
-            return raise_hip(e);
-        }
-    }
-    p->stored = true;
-    return AWS_OP_SUCCESS;
+    return enc_plan_launch_stored_copy(p, device_input, device_output, output_capacity, device_offsets, device_stored, stream);
 }
 
 int aws_huffman_amd_encode_plan_stored_size(
@@ -1797,7 +1810,7 @@ static int dec_plan_fill(
     p->n_items = p->n_chunks = p->n_large = p->n_runs = p->n_tail = p->n_fixed = p->n_wide = 0;
     p->quiet = false; /* (other items: nothing is known of what their launches list) */
     p->launches_with_chunks = 0; /* (... and no launch of these has left a summary to read it from) */
-    p->packed = p->packed_sized = p->stored = false;
+    p->packed = p->packed_sized = p->stored = p->stored_ranges = false;
     p->longest_in_len = 0;
     p->n_tiny = p->n_deep = 0;
     memset(&p->stats, 0, sizeof(p->stats));
@@ -2252,7 +2265,11 @@ static int dec_items_to_host(
         uint64_t *index = malloc((n_entries ? n_entries : 1) * sizeof(*index));
         uint64_t *at = malloc((n_offsets ? n_offsets : 1) * sizeof(*at));
         uint64_t *len = malloc((n_batch ? n_batch : 1) * sizeof(*len));
-        e = ranges && dir && index && at && len ? 0 : 2;
+        uint8_t *flag = calloc(n_batch ? n_batch : 1, 1); /* (all 0 without the sender's flags) */
+        e = ranges && dir && index && at && len && flag ? 0 : 2;
+        if (!e && n_items && n_batch && src->packed_stored) {
+            e = hufs_copy_d2h(flag, src->packed_stored, n_batch, st);
+        }
         if (!e && n_items) {
             e = hufs_copy_d2h(ranges, src->item_block_ranges, n_items * sizeof(*ranges), st);
         }
@@ -2283,8 +2300,19 @@ static int dec_items_to_host(
             const uint64_t off = at[item];
             const bool placed = src->packed_lengths || at[item + 1] >= off;
             const uint64_t bytes = src->packed_lengths ? len[item] : at[item + 1] - off;
-            if (next >= first && next < src->index_entries && next - first == blocks && b0 <= blocks && count <= blocks - b0 && placed &&
-                off <= src->encoded_length && bytes <= src->encoded_length - off) {
+            const bool framed = next >= first && next < src->index_entries && next - first == blocks && b0 <= blocks &&
+                                count <= blocks - b0 && placed && off <= src->encoded_length && bytes <= src->encoded_length - off;
+            if (flag[item] == 1) {
+                /* (an item stored raw: its bytes as they lie, nothing for the decode kernels, no index entry read) */
+                if (framed && bytes == symbols) {
+                    const uint64_t lo = b0 * src->block_symbols;
+                    const uint64_t hi = b0 + count == blocks ? symbols : lo + count * src->block_symbols;
+                    items[i].in_len = 0;
+                    items[i].in_offset = count ? src->encoded_offset + off + lo : 0;
+                    items[i].first_bit = 0;
+                    items[i].out_capacity = count ? hi - lo : 0;
+                }
+            } else if (flag[item] == 0 && framed) {
                 const uint64_t base = index[first], x0 = index[first + b0], x1 = index[first + b0 + count];
                 const uint64_t from = x0 - base, to = x1 - base;
                 const uint64_t first_byte = from / 8, end_byte = to / 8 + (to % 8 ? 1 : 0);
@@ -2302,6 +2330,7 @@ static int dec_items_to_host(
         free(index);
         free(at);
         free(len);
+        free(flag);
     } else if (src->kind == HUFD_ITEMS_ITEM_SYMBOL_RANGES) {
         /* (the directory and the offsets whole; load_item of plan_kernels.hip is the rule this loop restates) */
         const size_t n_batch = (size_t)src->batch_items;
@@ -2311,7 +2340,11 @@ static int dec_items_to_host(
         uint64_t *dir = malloc((n_batch + 1) * 2 * sizeof(*dir));
         uint64_t *at = malloc((n_offsets ? n_offsets : 1) * sizeof(*at));
         uint64_t *len = malloc((n_batch ? n_batch : 1) * sizeof(*len));
-        e = ranges && bits && dir && at && len ? 0 : 2;
+        uint8_t *flag = calloc(n_batch ? n_batch : 1, 1); /* (all 0 without the sender's flags) */
+        e = ranges && bits && dir && at && len && flag ? 0 : 2;
+        if (!e && n_items && n_batch && src->packed_stored) {
+            e = hufs_copy_d2h(flag, src->packed_stored, n_batch, st);
+        }
         if (!e && n_items) {
             e = hufs_copy_d2h(ranges, src->item_symbol_ranges, n_items * sizeof(*ranges), st);
         }
@@ -2342,9 +2375,12 @@ static int dec_items_to_host(
             const uint64_t bytes = src->packed_lengths ? len[item] : at[item + 1] - off;
             const uint64_t from = bits[2 * i], to = bits[2 * i + 1];
             const uint64_t first_byte = from / 8, end_byte = to / 8 + (to % 8 ? 1 : 0);
+            /* (an item stored raw: the locate body's closed form left the ends, a byte a symbol) */
+            const bool raw_ok =
+                flag[item] == 0 || (flag[item] == 1 && bytes == symbols && from % 8 == 0 && to - from == 8 * count);
             if (s0 <= symbols && count <= symbols - s0 && placed && off <= src->encoded_length && bytes <= src->encoded_length - off &&
-                from != HUFD_NO_BIT && to != HUFD_NO_BIT && to >= from && first_byte >= off && end_byte <= off + bytes) {
-                items[i].in_len = count ? end_byte - first_byte : 0;
+                from != HUFD_NO_BIT && to != HUFD_NO_BIT && to >= from && first_byte >= off && end_byte <= off + bytes && raw_ok) {
+                items[i].in_len = count && !flag[item] ? end_byte - first_byte : 0;
                 items[i].in_offset = count ? src->encoded_offset + first_byte : 0;
                 items[i].first_bit = count ? (uint8_t)(from % 8) : 0;
                 items[i].out_capacity = count;
@@ -2355,6 +2391,7 @@ static int dec_items_to_host(
         free(dir);
         free(at);
         free(len);
+        free(flag);
     } else {
         struct hufd_enc_item *ei = malloc((n_items ? n_items : 1) * sizeof(*ei));
         struct hufd_enc_result *er = malloc((n_items ? n_items : 1) * sizeof(*er));
@@ -2407,7 +2444,7 @@ static int dec_plan_fill_on_device(struct aws_huffman_amd_decode_plan *p, const 
     p->n_items = p->n_chunks = p->n_large = p->n_runs = p->n_tail = p->n_fixed = p->n_wide = 0;
     p->quiet = false; /* (other items: nothing is known of what their launches list) */
     p->launches_with_chunks = 0; /* (... and no launch of these has left a summary to read it from) */
-    p->packed = p->packed_sized = p->stored = false;
+    p->packed = p->packed_sized = p->stored = p->stored_ranges = false;
     p->longest_in_len = 0;
     p->n_tiny = p->n_deep = 0;
     memset(&p->stats, 0, sizeof(p->stats));
@@ -2608,6 +2645,11 @@ static void dec_plan_launch_args(
         a.few_walks = road & AWS_HUFFMAN_AMD_TEST_DECODE_LONG_WAY ? 0u : 1u;
     }
     a.stage_events = stage_events;
+    if (p->stored_ranges) { /* (a plain launch copies them; a packed one is refused in front of this) */
+        a.stored_rec = p->d_stored_rec;
+        a.stored_tile_first = p->d_stored_tile_first;
+        a.stored_tiles = p->stored_tiles;
+    }
     *args = a;
 }
 
@@ -2681,7 +2723,7 @@ int aws_huffman_amd_decode_plan_launch_packed(
         (!device_output && output_capacity)) {
         return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
     }
-    if (engine_never_fitted(p->engine)) {
+    if (engine_never_fitted(p->engine) || p->stored_ranges) { /* (ranges of stored items go where their ranges say: such a plan is for plain launches) */
         return aws_raise_error(AWS_ERROR_INVALID_STATE);
     }
     void *st = stream ? stream : p->engine->stream;
@@ -2816,6 +2858,50 @@ static int dec_plan_reserve_stored(struct aws_huffman_amd_decode_plan *p, size_t
     return 0;
 }
 
+/* What the launches of a plan with stored items need: {source offset, length} of every stored item -- from the three arrays
+ * of a packed input, or (ranges != NULL) from the item records of a plan of ranges and the batch's flags --, and the tiles the
+ * copy cuts the long ones into, scanned; their number comes back (the reset has waited for the planner's totals already).
+ * What fails leaves a plan without items. */
+static int dec_plan_stored_records(
+    struct aws_huffman_amd_decode_plan *p,
+    const uint64_t *device_offsets,
+    const uint64_t *device_lengths,
+    const uint8_t *device_stored,
+    const void *device_ranges,
+    void *stream) {
+
+    void *st = stream ? stream : p->engine->stream;
+    const uint32_t tile_items = hufk_pack_tile_items(p->n_items, __atomic_load_n(&s_pack_tile_items, __ATOMIC_RELAXED));
+    uint64_t tiles = 0;
+    ON_DEVICE(p->engine->device);
+    int e = dec_plan_reserve_stored(p, p->n_items, hufk_pack_tiles(p->n_items, tile_items));
+    if (!e) {
+        e = device_ranges
+                ? hufk_stored_range_records((const uint64_t *)device_ranges, device_stored, p->d_items, p->n_items, p->d_stored_rec, st)
+                : hufk_stored_records(device_offsets, device_lengths, device_stored, p->n_items, p->d_stored_rec, st);
+    }
+    if (!e) {
+        e = hufk_stored_tiles(
+            p->d_stored_rec, p->n_items, tile_items, HUFK_STORED_TILE_BYTES, HUFK_STORED_WAVE_BYTES, p->d_stored_tile_sums,
+            p->d_stored_tile_first, st);
+    }
+    if (!e) {
+        e = hufs_copy_d2h(&tiles, p->d_stored_tile_first + p->n_items, sizeof(tiles), st);
+    }
+    if (!e) {
+        e = hufs_stream_sync(st);
+    }
+    if (e || tiles >= 0x7FFFFFFFull) {
+        p->n_items = p->n_chunks = p->n_large = p->n_runs = p->n_tail = p->n_tiny = p->n_deep = p->n_fixed = p->n_wide = 0; /* (no plan) */
+        p->n_tail_narrow = 0;
+        p->packed = p->packed_sized = false;
+        memset(&p->stats, 0, sizeof(p->stats));
+        return e ? raise_hip(e) : aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    p->stored_tiles = tiles;
+    return AWS_OP_SUCCESS;
+}
+
 int aws_huffman_amd_decode_plan_reset_packed_stored_input(
     struct aws_huffman_amd_decode_plan *p,
     const uint64_t *device_offsets,
@@ -2848,35 +2934,9 @@ int aws_huffman_amd_decode_plan_reset_packed_stored_input(
     if (p->n_items == 0) {
         return AWS_OP_SUCCESS;
     }
-    /* what the launches need of the three arrays: {source offset, length} of every stored item, and the tiles the copy cuts
-     * the long ones into, scanned; their number comes back (the reset has waited for the planner's totals already) */
-    void *st = stream ? stream : p->engine->stream;
-    const uint32_t tile_items = hufk_pack_tile_items(p->n_items, __atomic_load_n(&s_pack_tile_items, __ATOMIC_RELAXED));
-    uint64_t tiles = 0;
-    ON_DEVICE(p->engine->device);
-    int e = dec_plan_reserve_stored(p, p->n_items, hufk_pack_tiles(p->n_items, tile_items));
-    if (!e) {
-        e = hufk_stored_records(device_offsets, device_lengths, device_stored, p->n_items, p->d_stored_rec, st);
+    if (dec_plan_stored_records(p, device_offsets, device_lengths, device_stored, NULL, stream)) {
+        return AWS_OP_ERR;
     }
-    if (!e) {
-        e = hufk_stored_tiles(
-            p->d_stored_rec, p->n_items, tile_items, HUFK_STORED_TILE_BYTES, HUFK_STORED_WAVE_BYTES, p->d_stored_tile_sums,
-            p->d_stored_tile_first, st);
-    }
-    if (!e) {
-        e = hufs_copy_d2h(&tiles, p->d_stored_tile_first + p->n_items, sizeof(tiles), st);
-    }
-    if (!e) {
-        e = hufs_stream_sync(st);
-    }
-    if (e || tiles >= 0x7FFFFFFFull) {
-        p->n_items = p->n_chunks = p->n_large = p->n_runs = p->n_tail = p->n_tiny = p->n_deep = p->n_fixed = p->n_wide = 0; /* (no plan) */
-        p->n_tail_narrow = 0;
-        p->packed = p->packed_sized = false;
-        memset(&p->stats, 0, sizeof(p->stats));
-        return e ? raise_hip(e) : aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
-    }
-    p->stored_tiles = tiles;
     p->stored = true;
     return AWS_OP_SUCCESS;
 }
@@ -3134,6 +3194,68 @@ int aws_huffman_amd_encode_plan_launch_packed_indexed(
     return enc_plan_launch_packed_items(p, device_input, device_output, stream);
 }
 
+/* ------------------------------------------------------------------ the same with items stored raw (huffman_amd_stored_index.h) */
+
+int aws_huffman_amd_encode_plan_launch_packed_stored_indexed(
+    struct aws_huffman_amd_encode_plan *p,
+    const void *device_input,
+    void *device_output,
+    uint64_t output_capacity,
+    uint64_t *device_offsets,
+    uint8_t *device_stored,
+    uint32_t align,
+    uint64_t block_symbols,
+    struct aws_huffman_amd_item_blocks *device_directory,
+    uint64_t *device_index,
+    uint64_t index_capacity,
+    uint32_t *device_status,
+    void *stream) {
+
+    if (hufs_device_count() <= 0) {
+        return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION); /* no GPU: there is no CPU path */
+    }
+    if (!packed_launch_args_ok(p, device_output, output_capacity, device_offsets, align) || !device_stored || !device_index ||
+        !block_index_args_ok(p, device_input, block_symbols, device_directory, device_index, index_capacity, device_status)) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    if (engine_never_fitted(p->engine)) {
+        return aws_raise_error(AWS_ERROR_INVALID_STATE);
+    }
+    uint32_t tile_items = 0;
+    if (p->n_items && enc_plan_packed_tile_items(p, &tile_items)) {
+        return AWS_OP_ERR;
+    }
+    /* the stages of an indexed launch with the scan that decides -- the coded lengths out of the index, flags, offsets, no room
+     * for a stored item in the second record array --, then the copy of the stored items behind the encode pass: one stream,
+     * the symbols read twice and the stored ones once more */
+    if (enc_plan_block_index_enqueue(p, device_input, block_symbols, device_directory, device_index, index_capacity, device_status, stream)) {
+        return AWS_OP_ERR;
+    }
+    void *st = stream ? stream : p->engine->stream;
+    if (p->n_items == 0) {
+        if (enc_plan_launch_packed_empty(p, device_offsets, st)) {
+            return AWS_OP_ERR;
+        }
+        p->stored = true;
+        ON_DEVICE(p->engine->device);
+        const int err = plan_mark_done(&p->done_event, &p->done_on_engine_stream, p->engine, stream);
+        return err ? raise_hip(err) : AWS_OP_SUCCESS;
+    }
+    {
+        ON_DEVICE(p->engine->device);
+        const int e = hufk_pack_offsets_stored_indexed(
+            p->d_items, p->n_items, tile_items, align, output_capacity, (const uint64_t *)device_directory, device_index, index_capacity,
+            p->d_pack_tile_sums, device_offsets, p->d_packed_items, p->d_pack_summary, device_stored, st);
+        if (e) {
+            return raise_hip(e);
+        }
+    }
+    if (enc_plan_launch_packed_items(p, device_input, device_output, stream)) {
+        return AWS_OP_ERR;
+    }
+    return enc_plan_launch_stored_copy(p, device_input, device_output, output_capacity, device_offsets, device_stored, stream);
+}
+
 int aws_huffman_amd_encode_plan_block_index_size(struct aws_huffman_amd_encode_plan *p, uint64_t *entries, void *stream) {
     if (!p || !entries || !p->block_indexed) {
         return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
@@ -3194,6 +3316,19 @@ _Static_assert(offsetof(struct aws_huffman_amd_item_block_range, first_block) ==
 _Static_assert(offsetof(struct aws_huffman_amd_item_block_range, block_count) == offsetof(struct hufd_item_block_range, block_count), "item block range layout");
 _Static_assert(offsetof(struct aws_huffman_amd_item_block_range, out_offset) == offsetof(struct hufd_item_block_range, out_offset), "item block range layout");
 
+/* a plan of ranges by item that was reset with the sender's flags: the records and tiles of the ranges in stored items, for
+ * the copy behind the emit stage of its plain launches */
+static int dec_plan_stored_ranges(struct aws_huffman_amd_decode_plan *p, const uint8_t *device_stored, const void *device_ranges, void *stream) {
+    if (!device_stored || p->n_items == 0) {
+        return AWS_OP_SUCCESS;
+    }
+    if (dec_plan_stored_records(p, NULL, NULL, device_stored, device_ranges, stream)) {
+        return AWS_OP_ERR;
+    }
+    p->stored_ranges = true;
+    return AWS_OP_SUCCESS;
+}
+
 int aws_huffman_amd_decode_plan_reset_item_block_ranges(
     struct aws_huffman_amd_decode_plan *p,
     const struct aws_huffman_amd_item_blocks *device_directory,
@@ -3203,6 +3338,26 @@ int aws_huffman_amd_decode_plan_reset_item_block_ranges(
     uint64_t block_symbols,
     const uint64_t *device_encoded_offsets,
     const uint64_t *device_encoded_lengths,
+    uint64_t encoded_offset,
+    uint64_t encoded_length,
+    const struct aws_huffman_amd_item_block_range *device_ranges,
+    size_t range_count,
+    void *stream) {
+    return aws_huffman_amd_decode_plan_reset_stored_item_block_ranges(
+        p, device_directory, device_index, index_entries, item_count, block_symbols, device_encoded_offsets, device_encoded_lengths, NULL,
+        encoded_offset, encoded_length, device_ranges, range_count, stream);
+}
+
+int aws_huffman_amd_decode_plan_reset_stored_item_block_ranges(
+    struct aws_huffman_amd_decode_plan *p,
+    const struct aws_huffman_amd_item_blocks *device_directory,
+    const uint64_t *device_index,
+    uint64_t index_entries,
+    uint64_t item_count,
+    uint64_t block_symbols,
+    const uint64_t *device_encoded_offsets,
+    const uint64_t *device_encoded_lengths,
+    const uint8_t *device_stored,
     uint64_t encoded_offset,
     uint64_t encoded_length,
     const struct aws_huffman_amd_item_block_range *device_ranges,
@@ -3235,9 +3390,13 @@ int aws_huffman_amd_decode_plan_reset_item_block_ranges(
     src.block_symbols = block_symbols;
     src.packed_offsets = device_encoded_offsets;
     src.packed_lengths = device_encoded_lengths;
+    src.packed_stored = device_stored;
     src.encoded_offset = encoded_offset;
     src.encoded_length = encoded_length;
-    return dec_plan_fill_on_device(p, &src, range_count, stream);
+    if (dec_plan_fill_on_device(p, &src, range_count, stream)) {
+        return AWS_OP_ERR;
+    }
+    return dec_plan_stored_ranges(p, device_stored, device_ranges, stream);
 }
 
 /* ------------------------------------------------------------------ symbols of an indexed stream (huffman_amd_ranges.h) */
@@ -3401,6 +3560,7 @@ struct batch_place {
     uint64_t encoded_length;
     const uint64_t *directory, *index, *offsets, *lengths;
     uint64_t index_entries, item_count, block_symbols;
+    const uint8_t *stored; /* the sender's flags (huffman_amd_stored_index.h), or NULL */
 };
 
 static bool batch_place_ok(const struct batch_place *b) {
@@ -3425,6 +3585,7 @@ static int locate_items_enqueue(
     job.directory = b->directory;
     job.offsets = b->offsets;
     job.lengths = b->lengths;
+    job.stored = b->stored;
     job.item_count = b->item_count;
     job.index_entries = b->index_entries;
     job.count = count;
@@ -3457,12 +3618,36 @@ int aws_huffman_amd_locate_item_symbols(
     uint64_t *device_bits,
     uint32_t *device_status,
     void *stream) {
+    return aws_huffman_amd_locate_stored_item_symbols(
+        eng, device_encoded, encoded_length, device_directory, device_index, index_entries, item_count, block_symbols,
+        device_encoded_offsets, device_encoded_lengths, NULL, device_items, device_symbols, count, device_bits, device_status, stream);
+}
+
+int aws_huffman_amd_locate_stored_item_symbols(
+    struct aws_huffman_amd_engine *eng,
+    const void *device_encoded,
+    uint64_t encoded_length,
+    const struct aws_huffman_amd_item_blocks *device_directory,
+    const uint64_t *device_index,
+    uint64_t index_entries,
+    uint64_t item_count,
+    uint64_t block_symbols,
+    const uint64_t *device_encoded_offsets,
+    const uint64_t *device_encoded_lengths,
+    const uint8_t *device_stored,
+    const uint64_t *device_items,
+    const uint64_t *device_symbols,
+    size_t count,
+    uint64_t *device_bits,
+    uint32_t *device_status,
+    void *stream) {
 
     if (hufs_device_count() <= 0) {
         return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION); /* no GPU: there is no CPU path */
     }
     const struct batch_place place = {device_encoded, encoded_length, (const uint64_t *)device_directory, device_index,
-                                      device_encoded_offsets, device_encoded_lengths, index_entries, item_count, block_symbols};
+                                      device_encoded_offsets, device_encoded_lengths, index_entries, item_count, block_symbols,
+                                      device_stored};
     if (!eng || !batch_place_ok(&place) || ((uintptr_t)device_status & 3u) || (encoded_length && !device_encoded) ||
         (count && (!device_items || !device_symbols || !device_bits)) || ((uintptr_t)device_items & 7u) ||
         ((uintptr_t)device_symbols & 7u) || ((uintptr_t)device_bits & 7u)) {
@@ -3495,6 +3680,27 @@ int aws_huffman_amd_decode_plan_reset_item_symbol_ranges(
     const struct aws_huffman_amd_item_symbol_range *device_ranges,
     size_t range_count,
     void *stream) {
+    return aws_huffman_amd_decode_plan_reset_stored_item_symbol_ranges(
+        p, device_input, device_directory, device_index, index_entries, item_count, block_symbols, device_encoded_offsets,
+        device_encoded_lengths, NULL, encoded_offset, encoded_length, device_ranges, range_count, stream);
+}
+
+int aws_huffman_amd_decode_plan_reset_stored_item_symbol_ranges(
+    struct aws_huffman_amd_decode_plan *p,
+    const void *device_input,
+    const struct aws_huffman_amd_item_blocks *device_directory,
+    const uint64_t *device_index,
+    uint64_t index_entries,
+    uint64_t item_count,
+    uint64_t block_symbols,
+    const uint64_t *device_encoded_offsets,
+    const uint64_t *device_encoded_lengths,
+    const uint8_t *device_stored,
+    uint64_t encoded_offset,
+    uint64_t encoded_length,
+    const struct aws_huffman_amd_item_symbol_range *device_ranges,
+    size_t range_count,
+    void *stream) {
 
     if (hufs_device_count() <= 0) {
         return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION);
@@ -3511,7 +3717,7 @@ int aws_huffman_amd_decode_plan_reset_item_symbol_ranges(
     src.kind = HUFD_ITEMS_ITEM_SYMBOL_RANGES;
     const struct batch_place place = {(const uint8_t *)device_input + encoded_offset, encoded_length, (const uint64_t *)device_directory,
                                       device_index, device_encoded_offsets, device_encoded_lengths, index_entries, item_count,
-                                      block_symbols};
+                                      block_symbols, device_stored};
     if (!batch_place_ok(&place) || (!device_ranges && range_count) || ((uintptr_t)device_ranges & 7u) || (!device_input && range_count) ||
         range_count >= 0xFFFFFFFFull) {
         const int rc = dec_plan_fill_on_device(p, &src, 0, stream); /* (a plan without items, as a refused range leaves it) */
@@ -3546,9 +3752,13 @@ int aws_huffman_amd_decode_plan_reset_item_symbol_ranges(
     src.block_symbols = block_symbols;
     src.packed_offsets = device_encoded_offsets;
     src.packed_lengths = device_encoded_lengths;
+    src.packed_stored = device_stored;
     src.encoded_offset = encoded_offset;
     src.encoded_length = encoded_length;
-    return dec_plan_fill_on_device(p, &src, range_count, stream);
+    if (dec_plan_fill_on_device(p, &src, range_count, stream)) {
+        return AWS_OP_ERR;
+    }
+    return dec_plan_stored_ranges(p, device_stored, device_ranges, stream);
 }
 
 /*
@@ -3708,7 +3918,7 @@ int aws_huffman_amd_decode_plan_from_encode(
     p->n_items = p->n_chunks = p->n_large = p->n_runs = p->n_tail = p->n_fixed = p->n_wide = 0;
     p->quiet = false; /* (other items: nothing is known of what their launches list) */
     p->launches_with_chunks = 0; /* (... and no launch of these has left a summary to read it from) */
-    p->packed = p->packed_sized = p->stored = false;
+    p->packed = p->packed_sized = p->stored = p->stored_ranges = false;
     p->longest_in_len = 0;
     p->n_tiny = p->n_deep = 0;
     memset(&p->stats, 0, sizeof(p->stats));

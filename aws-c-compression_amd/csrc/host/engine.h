@@ -204,6 +204,10 @@ struct aws_huffman_amd_decode_plan {
      * items stored raw have no encoded bytes in d_items; ONE allocation holds {source offset, length or HUFK_NOT_STORED} of
      * every item, the tiles of the copy in front of each item and the tile sums of their scan */
     bool stored;
+    /* a plan of ranges of an indexed batch reset with the sender's flags (huffman_amd_stored_index.h): a range in a stored item
+     * has no encoded bytes in d_items either, but a place of its own; the same allocation holds the same records and tiles, of
+     * the ranges, and a PLAIN launch copies them (a packed one is refused) */
+    bool stored_ranges;
     void *d_stored_arena;
     uint64_t *d_stored_rec;        /* [cap_stored_items][2] */
     uint64_t *d_stored_tile_first; /* [cap_stored_items + 1] */

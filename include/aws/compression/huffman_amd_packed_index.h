@@ -14,6 +14,8 @@
  * `entries` is an upper bound of the blocks plus one (sum of ceil(in_len / block_symbols) + 1), or what a size query through
  * aws_huffman_amd_encode_plan_block_index and aws_huffman_amd_encode_plan_block_index_size has said.
  *
+ * The same call for a batch that stores an item raw when its code does not shrink it: huffman_amd_stored_index.h.
+ *
  * Out of this interface: an index made by a PLAIN launch (aws_huffman_amd_encode_plan_launch), and aws_huffman_amd_shards_*.
  */
 

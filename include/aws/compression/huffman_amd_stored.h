@@ -14,8 +14,9 @@
  *
  * Known cost: the encode pass still reads and codes the symbols of a stored item and throws the result away.
  *
- * Out of this interface: aws_huffman_amd_encode_plan_launch_packed_indexed, the batch index and the range plans,
- * aws_huffman_amd_shards_*, the host-pointer calls, coders with symbols without a code made total.
+ * With the batch's block index and ranges into stored and coded items alike: huffman_amd_stored_index.h.
+ *
+ * Out of this interface: aws_huffman_amd_shards_*, the host-pointer calls, coders with symbols without a code made total.
  */
 
 #include <aws/compression/huffman_amd_packed.h>
