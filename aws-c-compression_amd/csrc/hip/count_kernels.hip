@@ -16,11 +16,13 @@
  * The same kernel has a second body, chosen by a launch argument: the hot pass of the block index (index_block_bits.hpp,
  * hufk_block_bits below), which reads the same bytes the same way and looks code lengths up where this one counts -- and a
  * third, the same pass over the items of a batch (index_batch_bits, hufk_batch_block_bits).  The fourth counts again: the
- * symbols of the items of an encode plan, into the same histogram (count_plan_items, hufk_plan_symbol_counts).
+ * symbols of the items of an encode plan, into the same histogram (count_plan_items, hufk_plan_symbol_counts).  The fifth
+ * splits elements of 2, 4 or 8 bytes into byte planes and counts every plane in that read (planes.hpp, hufk_planes_split).
  */
 #include "kernels_common.hpp"
 #include "index_block_bits.hpp"
 #include "launch_common.hpp"
+#include "planes.hpp"
 
 namespace {
 
@@ -172,7 +174,11 @@ __device__ __forceinline__ void count_plan_items(const index_job &job, u64 *coun
 __global__ __launch_bounds__(kCountThreads) void count_kernel(
     const u8 *head, u32 head_len, const uint4 *body, u64 n_vec, const u8 *tail, u32 tail_len, u64 *counts,
     u64 steps_per_flush, index_job index) {
-    if (index.index) { /* (the same in every thread of the launch) */
+    if (index.plane_bytes) { /* (the same in every thread of the launch) */
+        planes_split(index.in, index.planes, index.length, index.block_symbols, index.plane_bytes, counts, (u32)steps_per_flush);
+        return;
+    }
+    if (index.index) {
         if (index.items) {
             index_batch_bits(index);
         } else {
@@ -253,6 +259,35 @@ int hufk_symbol_counts(const void *input, uint64_t length, uint64_t *counts, uin
         count_kernel, dim3(grid), dim3(kCountThreads), kCountLdsBytes, (hipStream_t)stream, in, (u32)head_len,
         reinterpret_cast<const uint4 *>(in + head_len), n_vec, in + head_len + n_vec * 16u, (u32)tail_len, counts, per_flush,
         index_job{});
+    return (int)hipGetLastError();
+}
+
+int hufk_planes_split(
+    const void *input, uint64_t element_count, uint32_t element_bytes, void *planes, uint64_t plane_stride, uint64_t *counts,
+    uint64_t flush_bytes, uint32_t grid_cap, void *stream) {
+    static_assert(kPlanesSplitThreads == kCountThreads && kPlanesSplitStepBytes == kCountStepBytes, "hosted by count_kernel");
+    if (element_count == 0) {
+        return 0;
+    }
+    index_job job{};
+    job.in = (const u8 *)input;
+    job.planes = (u8 *)planes;
+    job.length = element_count;
+    job.block_symbols = plane_stride;
+    job.plane_bytes = element_bytes;
+    /* (a step is 32 KiB of elements whatever their size; fewer elements than a group's still need workgroup 0) */
+    const u64 step_elements = kPlanesSplitStepBytes / element_bytes;
+    const u64 steps = (element_count + step_elements - 1) / step_elements;
+    /* the grid is what is resident with the LDS this launch really uses: none without the counts */
+    const u32 lds_bytes = counts ? planes_hist_bytes(element_bytes) : 0u;
+    uint32_t grid = hufk_host::persistent_grid(
+        count_kernel, kCountThreads, lds_bytes, (uint32_t)(steps < 0xFFFFFFFFull ? steps : 0xFFFFFFFFull));
+    grid = grid_cap && grid_cap < grid ? grid_cap : grid;
+    u64 per_flush = flush_bytes / kCountStepBytes;
+    per_flush = per_flush ? (per_flush < 0xFFFFFFFFull ? per_flush : 0xFFFFFFFFull) : 1;
+    hipLaunchKernelGGL(
+        count_kernel, dim3(grid), dim3(kCountThreads), lds_bytes, (hipStream_t)stream, (const u8 *)nullptr, 0u, (const uint4 *)nullptr,
+        (u64)0, (const u8 *)nullptr, 0u, counts, per_flush, job);
     return (int)hipGetLastError();
 }
 

@@ -50,11 +50,16 @@ constexpr u64 kIndexHole = 1ull << 63; /* on a tile's first entry, between this 
  * kernel holds every word of this argument in a scalar register, and more of them would cost the other bodies.  Its four
  * small numbers lie on length and block_symbols, which the kernel loads at its entry for every body: on the four words
  * behind them, which only the index loads, the build had 81 scalar registers -- one band of residency lost -- and has 78 so.
+ *
+ * plane_bytes != 0: the launch splits elements into byte planes (planes_split, planes.hpp) -- `in` the elements, `planes`
+ * where the planes go, length the elements, block_symbols the plane stride; the counts and the steps between two flushes
+ * are the kernel's own arguments.  The word was padding: no body got a word to hold.
  */
 struct index_job {
     union {
         const u64 *enc_table;
         const u32 *tiny; /* (count) the plan's items a thread encodes: n_tiny numbers of items[] */
+        u8 *planes;      /* (planes) where the planes go */
     };
     const u8 *in;
     union {
@@ -69,7 +74,8 @@ struct index_job {
             u32 n_tiny, round_steps; /* (count) steps of a turn: what the plan's longest unit takes, see count_plan_items */
         };
     };
-    u32 groups_per_block, inverse, tile_blocks, pad;
+    u32 groups_per_block, inverse, tile_blocks;
+    u32 plane_bytes; /* not 0: the launch splits elements of that many bytes into planes (planes.hpp) */
     u64 n_tiles, n_blocks;
     u64 *index;
     /* the index of a batch (index_batch_bits below; items == nullptr: one stream): `in` is the input base of the plan's

@@ -128,6 +128,9 @@ struct __attribute__((packed, aligned(1))) unaligned_uint4 {
 struct __attribute__((packed, aligned(1))) unaligned_u32 {
     u32 x;
 };
+struct __attribute__((packed, aligned(1))) unaligned_uint2 {
+    u32 x, y;
+};
 
 __device__ __forceinline__ u32 round16(u32 x) {
     return (x + 15u) & ~15u;
@@ -195,6 +198,21 @@ __device__ __forceinline__ u32 funnel(u32 hi, u32 lo, u32 shift /* 0..31 */) {
     return __builtin_amdgcn_alignbit(hi, lo, shift);
 #else
     return (u32)(((((u64)hi) << 32) | lo) >> shift);
+#endif
+}
+
+/* four bytes picked from the eight of {hi, lo} -- lo's are numbers 0 .. 3, hi's 4 .. 7 --, result byte i by the selector's
+ * byte i (v_perm_b32; selectors above 7 mean other things there and are not used) */
+__device__ __forceinline__ u32 byte_perm(u32 hi, u32 lo, u32 selector) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(hi, lo, selector);
+#else
+    const u64 both = ((u64)hi << 32) | lo;
+    u32 r = 0;
+    for (u32 i = 0; i < 4; ++i) {
+        r |= (u32)((both >> (8 * ((selector >> (8 * i)) & 7u))) & 0xFFu) << (8 * i);
+    }
+    return r;
 #endif
 }
 

@@ -31,6 +31,7 @@
  */
 #include "kernels_common.hpp"
 #include "launch_common.hpp"
+#include "planes.hpp"
 
 namespace {
 
@@ -423,10 +424,11 @@ __global__ __launch_bounds__(kPackThreads) void pack_offsets_kernel(
 }
 
 #include "stored_copy.hpp"
+static_assert(kPlanesMergeThreads == kPackThreads, "planes_merge is hosted by unpack_records_kernel");
 
 /* what unpack_records_kernel is given where it runs a pass of the scan with the batch kinds (pass 0: it does not) */
 struct pack_scan {
-    u32 pass; /* 1: the tile sums, 2: the offsets, 3: the copy of items stored raw (stored_copy.hpp) */
+    u32 pass; /* 1: the tile sums, 2: the offsets, 3: the copy of items stored raw (stored_copy.hpp), 4: byte planes merged (planes.hpp) */
     u32 unused;
     union { /* (a launch is a pass of the scan or the copy, never both: the copy's job shares the scan's words) */
         struct {
@@ -440,6 +442,7 @@ struct pack_scan {
             void *packed;
         };
         stored_job stored; /* pass 3 */
+        planes_job planes; /* pass 4 */
     };
 };
 
@@ -453,6 +456,10 @@ __global__ __launch_bounds__(kPackThreads) void unpack_records_kernel(
     pack_scan scan) {
     if (scan.pass == 3) {
         stored_copy_body(scan.stored);
+        return;
+    }
+    if (scan.pass == 4) {
+        planes_merge(scan.planes);
         return;
     }
     if (scan.pass == 1) {
@@ -787,6 +794,30 @@ int hufk_stored_copy_decode(
     job.placed = placed;
     job.dec_results = results;
     stored_launch(job, (u32)blocks, (hipStream_t)stream);
+    return (int)hipGetLastError();
+}
+
+int hufk_planes_merge(
+    const void *planes, uint64_t plane_stride, uint64_t element_count, uint32_t element_bytes, void *output, uint32_t grid_cap,
+    void *stream) {
+    if (element_count == 0) {
+        return 0;
+    }
+    pack_scan scan{};
+    scan.pass = 4;
+    scan.planes.planes = (const u8 *)planes;
+    scan.planes.out = (u8 *)output;
+    scan.planes.n = element_count;
+    scan.planes.stride = plane_stride;
+    scan.planes.element_bytes = element_bytes;
+    const u64 step_elements = kPlanesMergeStepBytes / element_bytes;
+    const u64 steps = (element_count + step_elements - 1) / step_elements;
+    uint32_t grid = hufk_host::persistent_grid(
+        unpack_records_kernel, kPackThreads, 0, (uint32_t)(steps < 0xFFFFFFFFull ? steps : 0xFFFFFFFFull));
+    grid = grid_cap && grid_cap < grid ? grid_cap : grid;
+    hipLaunchKernelGGL(
+        unpack_records_kernel, dim3(grid), dim3(kPackThreads), 0, (hipStream_t)stream, (const hufd_dec_item *)nullptr,
+        (hufd_dec_item *)nullptr, (const hufd_chunk_rec *)nullptr, (hufd_chunk_rec *)nullptr, 0u, scan);
     return (int)hipGetLastError();
 }
 

@@ -14,6 +14,7 @@
 #include <aws/compression/huffman_amd_index.h>
 #include <aws/compression/huffman_amd_packed.h>
 #include <aws/compression/huffman_amd_plan_counts.h>
+#include <aws/compression/huffman_amd_planes.h>
 #include <aws/compression/huffman_amd_ranges.h>
 #include <aws/compression/huffman_amd_stored.h>
 #include <aws/compression/huffman_amd_stored_index.h>
@@ -4400,6 +4401,89 @@ int aws_huffman_amd_encode_plan_symbol_counts(
     if (!err) {
         /* (the plan's records are read on this stream: whoever gets its arrays next waits, as for a launch) */
         err = plan_mark_done(&p->done_event, &p->done_on_engine_stream, eng, stream);
+    }
+    return err ? raise_hip(err) : AWS_OP_SUCCESS;
+}
+
+/* Byte planes (huffman_amd_planes.h): what both calls check on the host, and the enqueue -- one launch, nothing made for it */
+static uint32_t s_planes_grid = 0;
+
+void aws_huffman_amd_testing_set_planes_grid(uint32_t workgroups) {
+    __atomic_store_n(&s_planes_grid, workgroups, __ATOMIC_RELAXED);
+}
+
+/* the checks the two calls share.  1: go on, 0: nothing to do, -1: raised */
+static int planes_check(
+    int *device, const void *elements, const void *planes, uint64_t element_count, uint32_t element_bytes, uint64_t plane_stride) {
+    if (hufs_device_count() <= 0) {
+        return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION); /* no GPU: there is no CPU path */
+    }
+    if (element_bytes != 1 && element_bytes != 2 && element_bytes != 4 && element_bytes != 8) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    if (element_count && (!elements || !planes)) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    if (plane_stride < element_count) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    /* n * E and (E - 1) * S + n fit 64 bits */
+    if (element_count > UINT64_MAX / element_bytes ||
+        (element_bytes > 1 && plane_stride > (UINT64_MAX - element_count) / (element_bytes - 1u))) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    if (*device < 0 && hufs_get_device(device)) {
+        return aws_raise_error(AWS_ERROR_UNKNOWN);
+    }
+    if (*device >= hufs_device_count()) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    if (element_count == 0) {
+        return 0;
+    }
+    /* the two ranges must not meet: [elements, + n * E) and [planes, + (E - 1) * S + n) */
+    const uint64_t a = (uint64_t)(uintptr_t)elements, a_len = element_count * element_bytes;
+    const uint64_t b = (uint64_t)(uintptr_t)planes, b_len = (uint64_t)(element_bytes - 1u) * plane_stride + element_count;
+    if (a_len > UINT64_MAX - a || b_len > UINT64_MAX - b || (a < b + b_len && b < a + a_len)) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    return 1;
+}
+
+int aws_huffman_amd_planes_split(
+    int device, const void *device_input, uint64_t element_count, uint32_t element_bytes, void *device_planes,
+    uint64_t plane_stride, uint64_t *device_counts, void *stream) {
+    if (hufs_device_count() > 0 && ((uintptr_t)device_counts & 7u)) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    const int go = planes_check(&device, device_input, device_planes, element_count, element_bytes, plane_stride);
+    if (go <= 0) {
+        return go;
+    }
+    ON_DEVICE(device);
+    int err = hufk_init(); /* the grid's size: the device's compute units */
+    if (!err) {
+        const uint64_t asked = __atomic_load_n(&s_count_flush_bytes, __ATOMIC_RELAXED);
+        err = hufk_planes_split(
+            device_input, element_count, element_bytes, device_planes, plane_stride, device_counts, asked ? asked : (1ull << 30),
+            __atomic_load_n(&s_planes_grid, __ATOMIC_RELAXED), stream);
+    }
+    return err ? raise_hip(err) : AWS_OP_SUCCESS;
+}
+
+int aws_huffman_amd_planes_merge(
+    int device, const void *device_planes, uint64_t plane_stride, uint64_t element_count, uint32_t element_bytes,
+    void *device_output, void *stream) {
+    const int go = planes_check(&device, device_output, device_planes, element_count, element_bytes, plane_stride);
+    if (go <= 0) {
+        return go;
+    }
+    ON_DEVICE(device);
+    int err = hufk_init();
+    if (!err) {
+        err = hufk_planes_merge(
+            device_planes, plane_stride, element_count, element_bytes, device_output, __atomic_load_n(&s_planes_grid, __ATOMIC_RELAXED),
+            stream);
     }
     return err ? raise_hip(err) : AWS_OP_SUCCESS;
 }
