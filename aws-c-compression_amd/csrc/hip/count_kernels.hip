@@ -263,8 +263,8 @@ int hufk_symbol_counts(const void *input, uint64_t length, uint64_t *counts, uin
 }
 
 int hufk_planes_split(
-    const void *input, uint64_t element_count, uint32_t element_bytes, void *planes, uint64_t plane_stride, uint64_t *counts,
-    uint64_t flush_bytes, uint32_t grid_cap, void *stream) {
+    const void *input, uint64_t element_count, uint32_t element_bytes, uint32_t run_elements, void *planes, uint64_t plane_stride,
+    uint64_t *counts, uint64_t flush_bytes, uint32_t grid_cap, void *stream) {
     static_assert(kPlanesSplitThreads == kCountThreads && kPlanesSplitStepBytes == kCountStepBytes, "hosted by count_kernel");
     if (element_count == 0) {
         return 0;
@@ -274,7 +274,7 @@ int hufk_planes_split(
     job.planes = (u8 *)planes;
     job.length = element_count;
     job.block_symbols = plane_stride;
-    job.plane_bytes = element_bytes;
+    job.plane_bytes = element_bytes | run_elements << kPlanesRunShift; /* (a run: at most 2048) */
     /* (a step is 32 KiB of elements whatever their size; fewer elements than a group's still need workgroup 0) */
     const u64 step_elements = kPlanesSplitStepBytes / element_bytes;
     const u64 steps = (element_count + step_elements - 1) / step_elements;

@@ -243,13 +243,16 @@ int hufk_plan_symbol_counts(
  *   _split   planes[p * plane_stride + j] = input[j * element_bytes + p], and with counts != NULL counts[p * 256 + b] += the
  *            bytes of plane p equal to b, the adds and flush_bytes as hufk_symbol_counts (a body of count_kernel)
  *   _merge   output[j * element_bytes + p] = planes[p * plane_stride + j] (a body of unpack_records_kernel)
- * One launch each, none for no elements.  grid_cap: the most workgroups (the tests'; 0: what is resident) */
+ * One launch each, none for no elements.  grid_cap: the most workgroups (the tests'; 0: what is resident)
+ * run_elements (0: as above; else a power of two from 16 to 2048, huffman_amd_planes_delta.h): the planes are those of
+ * d[j] = element j - element j - 1, d[j] = element j where run_elements divides j -- made by the split and counted, summed
+ * by the merge */
 int hufk_planes_split(
-    const void *input, uint64_t element_count, uint32_t element_bytes, void *planes, uint64_t plane_stride, uint64_t *counts,
-    uint64_t flush_bytes, uint32_t grid_cap, void *stream);
+    const void *input, uint64_t element_count, uint32_t element_bytes, uint32_t run_elements, void *planes, uint64_t plane_stride,
+    uint64_t *counts, uint64_t flush_bytes, uint32_t grid_cap, void *stream);
 int hufk_planes_merge(
-    const void *planes, uint64_t plane_stride, uint64_t element_count, uint32_t element_bytes, void *output, uint32_t grid_cap,
-    void *stream);
+    const void *planes, uint64_t plane_stride, uint64_t element_count, uint32_t element_bytes, uint32_t run_elements, void *output,
+    uint32_t grid_cap, void *stream);
 /* Between the length pass and the encode pass of a packed launch (pack_kernels.hip): from the length pass's records
  * `lengths`, offsets[i] = the sum of round_up((total_bits + 7) / 8, align) of the items in front of i, offsets[n_items] the
  * total; packed[i] = items[i] with out_off = offsets[i] and out_cap = what of the item's rounded length lies in front of

@@ -75,7 +75,8 @@ struct index_job {
         };
     };
     u32 groups_per_block, inverse, tile_blocks;
-    u32 plane_bytes; /* not 0: the launch splits elements of that many bytes into planes (planes.hpp) */
+    u32 plane_bytes; /* not 0: the launch splits elements of that many bytes (its low 8 bits) into planes, and above them the
+                      * run of a split of differences, 0 for the plain split (planes.hpp) */
     u64 n_tiles, n_blocks;
     u64 *index;
     /* the index of a batch (index_batch_bits below; items == nullptr: one stream): `in` is the input base of the plan's

@@ -428,7 +428,7 @@ static_assert(kPlanesMergeThreads == kPackThreads, "planes_merge is hosted by un
 
 /* what unpack_records_kernel is given where it runs a pass of the scan with the batch kinds (pass 0: it does not) */
 struct pack_scan {
-    u32 pass; /* 1: the tile sums, 2: the offsets, 3: the copy of items stored raw (stored_copy.hpp), 4: byte planes merged (planes.hpp) */
+    u32 pass; /* 1: the tile sums, 2: the offsets, 3: the copy of items stored raw (stored_copy.hpp), 4: byte planes merged, or their differences summed in runs (planes.hpp) */
     u32 unused;
     union { /* (a launch is a pass of the scan or the copy, never both: the copy's job shares the scan's words) */
         struct {
@@ -798,8 +798,8 @@ int hufk_stored_copy_decode(
 }
 
 int hufk_planes_merge(
-    const void *planes, uint64_t plane_stride, uint64_t element_count, uint32_t element_bytes, void *output, uint32_t grid_cap,
-    void *stream) {
+    const void *planes, uint64_t plane_stride, uint64_t element_count, uint32_t element_bytes, uint32_t run_elements, void *output,
+    uint32_t grid_cap, void *stream) {
     if (element_count == 0) {
         return 0;
     }
@@ -810,13 +810,16 @@ int hufk_planes_merge(
     scan.planes.n = element_count;
     scan.planes.stride = plane_stride;
     scan.planes.element_bytes = element_bytes;
+    scan.planes.run_elements = run_elements;
     const u64 step_elements = kPlanesMergeStepBytes / element_bytes;
     const u64 steps = (element_count + step_elements - 1) / step_elements;
+    /* sums of differences: the waves' totals of a run, and of the tail's base, go through LDS */
+    const u32 lds_bytes = run_elements ? kPlanesMergeSlotBytes : 0u;
     uint32_t grid = hufk_host::persistent_grid(
-        unpack_records_kernel, kPackThreads, 0, (uint32_t)(steps < 0xFFFFFFFFull ? steps : 0xFFFFFFFFull));
+        unpack_records_kernel, kPackThreads, lds_bytes, (uint32_t)(steps < 0xFFFFFFFFull ? steps : 0xFFFFFFFFull));
     grid = grid_cap && grid_cap < grid ? grid_cap : grid;
     hipLaunchKernelGGL(
-        unpack_records_kernel, dim3(grid), dim3(kPackThreads), 0, (hipStream_t)stream, (const hufd_dec_item *)nullptr,
+        unpack_records_kernel, dim3(grid), dim3(kPackThreads), lds_bytes, (hipStream_t)stream, (const hufd_dec_item *)nullptr,
         (hufd_dec_item *)nullptr, (const hufd_chunk_rec *)nullptr, (hufd_chunk_rec *)nullptr, 0u, scan);
     return (int)hipGetLastError();
 }

@@ -15,6 +15,7 @@
 #include <aws/compression/huffman_amd_packed.h>
 #include <aws/compression/huffman_amd_plan_counts.h>
 #include <aws/compression/huffman_amd_planes.h>
+#include <aws/compression/huffman_amd_planes_delta.h>
 #include <aws/compression/huffman_amd_ranges.h>
 #include <aws/compression/huffman_amd_stored.h>
 #include <aws/compression/huffman_amd_stored_index.h>
@@ -4450,9 +4451,10 @@ static int planes_check(
     return 1;
 }
 
-int aws_huffman_amd_planes_split(
-    int device, const void *device_input, uint64_t element_count, uint32_t element_bytes, void *device_planes,
-    uint64_t plane_stride, uint64_t *device_counts, void *stream) {
+/* the two calls and their twins over differences in runs (huffman_amd_planes_delta.h): run_elements 0 is the plain call */
+static int planes_split_any(
+    int device, const void *device_input, uint64_t element_count, uint32_t element_bytes, uint32_t run_elements,
+    void *device_planes, uint64_t plane_stride, uint64_t *device_counts, void *stream) {
     if (hufs_device_count() > 0 && ((uintptr_t)device_counts & 7u)) {
         return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
     }
@@ -4465,15 +4467,15 @@ int aws_huffman_amd_planes_split(
     if (!err) {
         const uint64_t asked = __atomic_load_n(&s_count_flush_bytes, __ATOMIC_RELAXED);
         err = hufk_planes_split(
-            device_input, element_count, element_bytes, device_planes, plane_stride, device_counts, asked ? asked : (1ull << 30),
-            __atomic_load_n(&s_planes_grid, __ATOMIC_RELAXED), stream);
+            device_input, element_count, element_bytes, run_elements, device_planes, plane_stride, device_counts,
+            asked ? asked : (1ull << 30), __atomic_load_n(&s_planes_grid, __ATOMIC_RELAXED), stream);
     }
     return err ? raise_hip(err) : AWS_OP_SUCCESS;
 }
 
-int aws_huffman_amd_planes_merge(
+static int planes_merge_any(
     int device, const void *device_planes, uint64_t plane_stride, uint64_t element_count, uint32_t element_bytes,
-    void *device_output, void *stream) {
+    uint32_t run_elements, void *device_output, void *stream) {
     const int go = planes_check(&device, device_output, device_planes, element_count, element_bytes, plane_stride);
     if (go <= 0) {
         return go;
@@ -4482,10 +4484,47 @@ int aws_huffman_amd_planes_merge(
     int err = hufk_init();
     if (!err) {
         err = hufk_planes_merge(
-            device_planes, plane_stride, element_count, element_bytes, device_output, __atomic_load_n(&s_planes_grid, __ATOMIC_RELAXED),
-            stream);
+            device_planes, plane_stride, element_count, element_bytes, run_elements, device_output,
+            __atomic_load_n(&s_planes_grid, __ATOMIC_RELAXED), stream);
     }
     return err ? raise_hip(err) : AWS_OP_SUCCESS;
+}
+
+int aws_huffman_amd_planes_split(
+    int device, const void *device_input, uint64_t element_count, uint32_t element_bytes, void *device_planes,
+    uint64_t plane_stride, uint64_t *device_counts, void *stream) {
+    return planes_split_any(device, device_input, element_count, element_bytes, 0, device_planes, plane_stride, device_counts, stream);
+}
+
+int aws_huffman_amd_planes_merge(
+    int device, const void *device_planes, uint64_t plane_stride, uint64_t element_count, uint32_t element_bytes,
+    void *device_output, void *stream) {
+    return planes_merge_any(device, device_planes, plane_stride, element_count, element_bytes, 0, device_output, stream);
+}
+
+/* a run: a power of two from 16 to 2048 -- a lane's group is 16 elements (8 of 8 bytes) and the merge's step 2048 elements of
+ * 8 bytes, so a run starts on a group and lies in one step.  (Without a GPU the answer is that there is none, whatever else.) */
+static bool planes_run_refused(uint32_t run_elements) {
+    return hufs_device_count() > 0 && (run_elements < 16 || run_elements > 2048 || (run_elements & (run_elements - 1)));
+}
+
+int aws_huffman_amd_plane_delta_split(
+    int device, const void *device_input, uint64_t element_count, uint32_t element_bytes, uint32_t run_elements,
+    void *device_planes, uint64_t plane_stride, uint64_t *device_counts, void *stream) {
+    if (planes_run_refused(run_elements)) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    return planes_split_any(
+        device, device_input, element_count, element_bytes, run_elements, device_planes, plane_stride, device_counts, stream);
+}
+
+int aws_huffman_amd_plane_delta_merge(
+    int device, const void *device_planes, uint64_t plane_stride, uint64_t element_count, uint32_t element_bytes,
+    uint32_t run_elements, void *device_output, void *stream) {
+    if (planes_run_refused(run_elements)) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    return planes_merge_any(device, device_planes, plane_stride, element_count, element_bytes, run_elements, device_output, stream);
 }
 
 int aws_huffman_amd_stream_synchronize(struct aws_huffman_amd_engine *eng, void *stream) {

@@ -31,6 +31,7 @@
  * AWS_ERROR_UNSUPPORTED_OPERATION without a GPU (nothing is read or written).
  *
  * Out of this interface: other element sizes, bit planes, a container for the per-plane buffers, host pointers.
+ * (Sorted and slowly moving integers -- offsets, running sums, ids: the planes of their differences, huffman_amd_planes_delta.h.)
  */
 
 #include <aws/compression/huffman_amd.h>
