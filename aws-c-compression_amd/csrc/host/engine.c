@@ -6,6 +6,7 @@
  * There is no CPU implementation of encode or decode here.
  */
 #include "engine.h"
+#include "arena.h"
 
 #include <aws/compression/huffman_amd_batch_index.h>
 #include <aws/compression/huffman_amd_packed_index.h>
@@ -104,6 +105,17 @@ static void device_scope_leave(struct device_scope *sc) {
 static int raise_hip(int hip_error) {
     (void)hip_error;
     return aws_raise_error(AWS_ERROR_UNKNOWN);
+}
+
+/* the few words a launch's scan left for the host (a plan's size getters): copied back on `st`, which is waited for.
+ * src NULL: nothing was left (a plan without items) -- the wait alone, the words stay as they are */
+static int plan_read_words(int device, const uint64_t *src, uint64_t *words, size_t n, void *st) {
+    ON_DEVICE(device);
+    int err = src ? hufs_copy_d2h(words, src, n * sizeof(uint64_t), st) : 0;
+    if (!err) {
+        err = hufs_stream_sync(st);
+    }
+    return err ? raise_hip(err) : AWS_OP_SUCCESS;
 }
 
 static void *device_upload(const void *host, size_t size, void *stream, int *err) {
@@ -679,14 +691,6 @@ static bool engine_never_fitted(const struct aws_huffman_amd_engine *eng) {
 
 /* ------------------------------------------------------------------ encode plans */
 
-/* A plan's device arrays are cuts of ONE allocation (a new plan paid some twenty-five hipMallocs: 1 .. 15 ms for
- * BASELINE configs[3], where filling it takes 0.5 ms): every array starts at a multiple of 256 bytes. */
-static size_t arena_cut(size_t *total, size_t bytes) {
-    const size_t at = (*total + 255u) & ~(size_t)255u;
-    *total = at + bytes;
-    return at;
-}
-
 #define ENC_PLAN_ARRAYS(X, ci, cs, cl, ct)                                                                                 \
     X(d_items, (ci) * sizeof(struct hufd_enc_item))                                                                    \
     X(d_segs, (cs) * sizeof(struct hufd_enc_seg))                                                                      \
@@ -817,18 +821,12 @@ static int enc_plan_reserve(struct aws_huffman_amd_encode_plan *p, size_t n_item
     if (n_items > p->cap_items || n_segs > p->cap_segs || n_large > p->cap_large || n_tiny > p->cap_tiny) {
         enc_plan_release_device(p);
         const size_t ci = n_items ? n_items : 1, cs = n_segs ? n_segs : 1, cl = n_large ? n_large : 1, ct = n_tiny ? n_tiny : 1;
-        size_t total = 0;
-#define ENC_SIZE(name, bytes) (void)arena_cut(&total, (bytes));
-        ENC_PLAN_ARRAYS(ENC_SIZE, ci, cs, cl, ct)
-#undef ENC_SIZE
-        p->d_arena = hufs_malloc(total);
-        if (!p->d_arena) {
+#define ENC_PART(name, bytes) {&p->name, (bytes)},
+        const struct arena_part parts[] = {ENC_PLAN_ARRAYS(ENC_PART, ci, cs, cl, ct)};
+#undef ENC_PART
+        if (arena_alloc(&p->d_arena, ARENA_PARTS(parts))) {
             return 2;
         }
-        total = 0;
-#define ENC_PLACE(name, bytes) p->name = (void *)((uint8_t *)p->d_arena + arena_cut(&total, (bytes)));
-        ENC_PLAN_ARRAYS(ENC_PLACE, ci, cs, cl, ct)
-#undef ENC_PLACE
         p->cap_items = ci;
         p->cap_segs = cs;
         p->cap_large = cl;
@@ -1304,21 +1302,15 @@ static int enc_plan_reserve_packed(struct aws_huffman_amd_encode_plan *p, size_t
     if (p->d_packed_arena && n_items <= p->cap_packed_items && n_tiles <= p->cap_pack_tiles) {
         return 0;
     }
-    hufs_free(p->d_packed_arena); /* (waits for what still reads it) */
-    p->d_packed_arena = NULL;
     p->cap_packed_items = p->cap_pack_tiles = 0;
     const size_t ci = n_items > p->cap_items ? n_items : p->cap_items; /* as many as the plan's own array: a reset within it allocates nothing */
-    size_t total = 0;
-    const size_t at_items = arena_cut(&total, ci * sizeof(struct hufd_enc_item));
-    const size_t at_sums = arena_cut(&total, 2 * n_tiles * sizeof(uint64_t));
-    const size_t at_summary = arena_cut(&total, 4 * sizeof(uint64_t)); /* (the last two: a stored launch's counts) */
-    p->d_packed_arena = hufs_malloc(total);
-    if (!p->d_packed_arena) {
+    const struct arena_part parts[] = {
+        {&p->d_packed_items, ci * sizeof(struct hufd_enc_item)},
+        {&p->d_pack_tile_sums, 2 * n_tiles * sizeof(uint64_t)},
+        {&p->d_pack_summary, 4 * sizeof(uint64_t)}}; /* (the last two: a stored launch's counts) */
+    if (arena_alloc(&p->d_packed_arena, ARENA_PARTS(parts))) {
         return 2;
     }
-    p->d_packed_items = (void *)((uint8_t *)p->d_packed_arena + at_items);
-    p->d_pack_tile_sums = (void *)((uint8_t *)p->d_packed_arena + at_sums);
-    p->d_pack_summary = (void *)((uint8_t *)p->d_packed_arena + at_summary);
     p->cap_packed_items = ci;
     p->cap_pack_tiles = n_tiles;
     return 0;
@@ -1332,80 +1324,22 @@ static bool packed_launch_args_ok(
            (device_output || !output_capacity);
 }
 
-/* a packed launch of a plan without items: offsets[0] = 0, and a size of nothing */
-static int enc_plan_launch_packed_empty(struct aws_huffman_amd_encode_plan *p, uint64_t *device_offsets, void *st) {
-    ON_DEVICE(p->engine->device);
-    const int e = hufs_memset(device_offsets, 0, sizeof(uint64_t), st);
-    if (e) {
-        return raise_hip(e);
-    }
-    p->packed = p->stored = false;
-    p->packed_sized = true;
-    return AWS_OP_SUCCESS;
-}
+/* what a launch that makes the batch's block index on the way is given for it (huffman_amd_packed_index.h), and
+ * aws_huffman_amd_encode_plan_block_index as well */
+struct enc_plan_index_args {
+    uint64_t block_symbols;
+    struct aws_huffman_amd_item_blocks *directory;
+    uint64_t *index;
+    uint64_t index_capacity;
+    uint32_t *status;
+};
+static bool enc_plan_block_index_args_ok(
+    const struct aws_huffman_amd_encode_plan *p, const void *device_input, const struct enc_plan_index_args *ix);
+static int enc_plan_block_index_enqueue(
+    struct aws_huffman_amd_encode_plan *p, const void *device_input, const struct enc_plan_index_args *ix, void *stream);
 
-/* the scan's tile for the plan's items, with the second record array and the scan's scratch reserved for them */
-static int enc_plan_packed_tile_items(struct aws_huffman_amd_encode_plan *p, uint32_t *tile_items) {
-    *tile_items = hufk_pack_tile_items(p->n_items, __atomic_load_n(&s_pack_tile_items, __ATOMIC_RELAXED));
-    ON_DEVICE(p->engine->device);
-    const int e = enc_plan_reserve_packed(p, p->n_items, hufk_pack_tiles(p->n_items, *tile_items));
-    return e ? raise_hip(e) : AWS_OP_SUCCESS;
-}
-
-/* the encode pass of a packed launch, over the second record array the scan has made */
-static int enc_plan_launch_packed_items(struct aws_huffman_amd_encode_plan *p, const void *device_input, void *device_output, void *stream) {
-    if (enc_plan_launch_items(p, p->d_packed_items, device_input, device_output, false, stream, NULL)) {
-        return AWS_OP_ERR;
-    }
-    p->packed = true;
-    p->packed_sized = true;
-    return AWS_OP_SUCCESS;
-}
-
-int aws_huffman_amd_encode_plan_launch_packed(
-    struct aws_huffman_amd_encode_plan *p,
-    const void *device_input,
-    void *device_output,
-    uint64_t output_capacity,
-    uint64_t *device_offsets,
-    uint32_t align,
-    void *stream) {
-
-    if (!packed_launch_args_ok(p, device_output, output_capacity, device_offsets, align)) {
-        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
-    }
-    if (engine_never_fitted(p->engine)) {
-        return aws_raise_error(AWS_ERROR_INVALID_STATE);
-    }
-    void *st = stream ? stream : p->engine->stream;
-    if (p->n_items == 0) {
-        return enc_plan_launch_packed_empty(p, device_offsets, st);
-    }
-    uint32_t tile_items = 0;
-    if (enc_plan_packed_tile_items(p, &tile_items)) {
-        return AWS_OP_ERR;
-    }
-    /* the lengths (into the plan's result records), the offsets and the second record array from them, the encode pass over
-     * that array (its records replace the lengths): three stages on one stream */
-    if (enc_plan_launch_items(p, p->d_items, device_input, device_output, true, stream, NULL)) {
-        return AWS_OP_ERR;
-    }
-    {
-        ON_DEVICE(p->engine->device);
-        const int e = hufk_pack_offsets(
-            p->d_items, p->d_results, p->n_items, tile_items, align, output_capacity, p->d_pack_tile_sums, device_offsets,
-            p->d_packed_items, p->d_pack_summary, st);
-        if (e) {
-            return raise_hip(e);
-        }
-    }
-    return enc_plan_launch_packed_items(p, device_input, device_output, stream);
-}
-
-/* ------------------------------------------------------------------ items stored raw, the sender (huffman_amd_stored.h) */
-
-/* the tail of a stored launch, behind the encode pass over the second record array: the copy of the stored items and their
- * records, and the plan's state */
+/* the tail of a stored launch (huffman_amd_stored.h), behind the encode pass over the second record array: the copy of the
+ * stored items and their records, and the plan's state */
 static int enc_plan_launch_stored_copy(
     struct aws_huffman_amd_encode_plan *p,
     const void *device_input,
@@ -1432,6 +1366,100 @@ static int enc_plan_launch_stored_copy(
     return AWS_OP_SUCCESS;
 }
 
+/*
+ * Every packed launch of an encode plan; the caller has checked the arguments.  Three stages on one stream:
+ *   - the lengths: a length pass into the plan's result records, or (ix) the batch's block index, whose hot pass reads the
+ *     symbols once and leaves the coded lengths in the index;
+ *   - the scan: the offsets and the second record array from those lengths; with `device_stored` it also decides which items
+ *     are stored raw, flags them and gives them no room in the second record array;
+ *   - the encode pass over that array (its records replace the lengths), and behind it the copy of the stored items.
+ */
+static int enc_plan_launch_packed_any(
+    struct aws_huffman_amd_encode_plan *p,
+    const void *device_input,
+    void *device_output,
+    uint64_t output_capacity,
+    uint64_t *device_offsets,
+    uint32_t align,
+    uint8_t *device_stored, /* NULL: no item is stored */
+    const struct enc_plan_index_args *ix, /* NULL: no index is made */
+    void *stream) {
+
+    if (engine_never_fitted(p->engine)) {
+        return aws_raise_error(AWS_ERROR_INVALID_STATE);
+    }
+    void *st = stream ? stream : p->engine->stream;
+    uint32_t tile_items = 0;
+    if (p->n_items) {
+        /* the scan's tile, with the second record array and the scan's scratch reserved: before anything is enqueued */
+        tile_items = hufk_pack_tile_items(p->n_items, __atomic_load_n(&s_pack_tile_items, __ATOMIC_RELAXED));
+        ON_DEVICE(p->engine->device);
+        const int e = enc_plan_reserve_packed(p, p->n_items, hufk_pack_tiles(p->n_items, tile_items));
+        if (e) {
+            return raise_hip(e);
+        }
+    }
+    /* (a plan without items still gets its index: the directory's one record, index[0] and the status) */
+    if (ix ? enc_plan_block_index_enqueue(p, device_input, ix, stream)
+           : (p->n_items && enc_plan_launch_items(p, p->d_items, device_input, device_output, true, stream, NULL))) {
+        return AWS_OP_ERR;
+    }
+    ON_DEVICE(p->engine->device);
+    if (p->n_items == 0) { /* offsets[0] = 0, and a size of nothing */
+        int e = hufs_memset(device_offsets, 0, sizeof(uint64_t), st);
+        if (e) {
+            return raise_hip(e);
+        }
+        p->packed = false;
+        p->packed_sized = true;
+        p->stored = device_stored != NULL;
+        /* (the index read the plan's records and scratch on this stream: whoever gets its arrays next waits, as for a launch) */
+        e = ix ? plan_mark_done(&p->done_event, &p->done_on_engine_stream, p->engine, stream) : 0;
+        return e ? raise_hip(e) : AWS_OP_SUCCESS;
+    }
+    const uint64_t *directory = ix ? (const uint64_t *)ix->directory : NULL;
+    const int e =
+        ix ? (device_stored ? hufk_pack_offsets_stored_indexed(
+                                  p->d_items, p->n_items, tile_items, align, output_capacity, directory, ix->index, ix->index_capacity,
+                                  p->d_pack_tile_sums, device_offsets, p->d_packed_items, p->d_pack_summary, device_stored, st)
+                            : hufk_pack_offsets_indexed(
+                                  p->d_items, p->n_items, tile_items, align, output_capacity, directory, ix->index, ix->index_capacity,
+                                  p->d_pack_tile_sums, device_offsets, p->d_packed_items, p->d_pack_summary, st))
+           : (device_stored ? hufk_pack_offsets_stored(
+                                  p->d_items, p->d_results, p->n_items, tile_items, align, output_capacity, p->d_pack_tile_sums,
+                                  device_offsets, p->d_packed_items, p->d_pack_summary, device_stored, st)
+                            : hufk_pack_offsets(
+                                  p->d_items, p->d_results, p->n_items, tile_items, align, output_capacity, p->d_pack_tile_sums,
+                                  device_offsets, p->d_packed_items, p->d_pack_summary, st));
+    if (e) {
+        return raise_hip(e);
+    }
+    if (enc_plan_launch_items(p, p->d_packed_items, device_input, device_output, false, stream, NULL)) {
+        return AWS_OP_ERR;
+    }
+    p->packed = true;
+    p->packed_sized = true;
+    if (!device_stored) {
+        return AWS_OP_SUCCESS;
+    }
+    return enc_plan_launch_stored_copy(p, device_input, device_output, output_capacity, device_offsets, device_stored, stream);
+}
+
+int aws_huffman_amd_encode_plan_launch_packed(
+    struct aws_huffman_amd_encode_plan *p,
+    const void *device_input,
+    void *device_output,
+    uint64_t output_capacity,
+    uint64_t *device_offsets,
+    uint32_t align,
+    void *stream) {
+
+    if (!packed_launch_args_ok(p, device_output, output_capacity, device_offsets, align)) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    return enc_plan_launch_packed_any(p, device_input, device_output, output_capacity, device_offsets, align, NULL, NULL, stream);
+}
+
 int aws_huffman_amd_encode_plan_launch_packed_stored(
     struct aws_huffman_amd_encode_plan *p,
     const void *device_input,
@@ -1445,39 +1473,58 @@ int aws_huffman_amd_encode_plan_launch_packed_stored(
     if (!packed_launch_args_ok(p, device_output, output_capacity, device_offsets, align) || !device_stored) {
         return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
     }
-    if (engine_never_fitted(p->engine)) {
-        return aws_raise_error(AWS_ERROR_INVALID_STATE);
+    return enc_plan_launch_packed_any(p, device_input, device_output, output_capacity, device_offsets, align, device_stored, NULL, stream);
+}
+
+int aws_huffman_amd_encode_plan_launch_packed_indexed(
+    struct aws_huffman_amd_encode_plan *p,
+    const void *device_input,
+    void *device_output,
+    uint64_t output_capacity,
+    uint64_t *device_offsets,
+    uint32_t align,
+    uint64_t block_symbols,
+    struct aws_huffman_amd_item_blocks *device_directory,
+    uint64_t *device_index,
+    uint64_t index_capacity,
+    uint32_t *device_status,
+    void *stream) {
+
+    const struct enc_plan_index_args ix = {block_symbols, device_directory, device_index, index_capacity, device_status};
+    if (hufs_device_count() <= 0) {
+        return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION); /* no GPU: there is no CPU path */
     }
-    void *st = stream ? stream : p->engine->stream;
-    if (p->n_items == 0) {
-        if (enc_plan_launch_packed_empty(p, device_offsets, st)) {
-            return AWS_OP_ERR;
-        }
-        p->stored = true;
-        return AWS_OP_SUCCESS;
+    if (!packed_launch_args_ok(p, device_output, output_capacity, device_offsets, align) || !device_index ||
+        !enc_plan_block_index_args_ok(p, device_input, &ix)) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
     }
-    uint32_t tile_items = 0;
-    if (enc_plan_packed_tile_items(p, &tile_items)) {
-        return AWS_OP_ERR;
+    return enc_plan_launch_packed_any(p, device_input, device_output, output_capacity, device_offsets, align, NULL, &ix, stream);
+}
+
+int aws_huffman_amd_encode_plan_launch_packed_stored_indexed(
+    struct aws_huffman_amd_encode_plan *p,
+    const void *device_input,
+    void *device_output,
+    uint64_t output_capacity,
+    uint64_t *device_offsets,
+    uint8_t *device_stored,
+    uint32_t align,
+    uint64_t block_symbols,
+    struct aws_huffman_amd_item_blocks *device_directory,
+    uint64_t *device_index,
+    uint64_t index_capacity,
+    uint32_t *device_status,
+    void *stream) {
+
+    const struct enc_plan_index_args ix = {block_symbols, device_directory, device_index, index_capacity, device_status};
+    if (hufs_device_count() <= 0) {
+        return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION); /* no GPU: there is no CPU path */
     }
-    /* a packed launch's three stages with the scan that decides -- lengths, flags, offsets, no room for a stored item in the
-     * second record array --, then the copy of the stored items and their records behind the encode pass: one stream */
-    if (enc_plan_launch_items(p, p->d_items, device_input, device_output, true, stream, NULL)) {
-        return AWS_OP_ERR;
+    if (!packed_launch_args_ok(p, device_output, output_capacity, device_offsets, align) || !device_stored || !device_index ||
+        !enc_plan_block_index_args_ok(p, device_input, &ix)) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
     }
-    {
-        ON_DEVICE(p->engine->device);
-        const int e = hufk_pack_offsets_stored(
-            p->d_items, p->d_results, p->n_items, tile_items, align, output_capacity, p->d_pack_tile_sums, device_offsets,
-            p->d_packed_items, p->d_pack_summary, device_stored, st);
-        if (e) {
-            return raise_hip(e);
-        }
-    }
-    if (enc_plan_launch_packed_items(p, device_input, device_output, stream)) {
-        return AWS_OP_ERR;
-    }
-    return enc_plan_launch_stored_copy(p, device_input, device_output, output_capacity, device_offsets, device_stored, stream);
+    return enc_plan_launch_packed_any(p, device_input, device_output, output_capacity, device_offsets, align, device_stored, &ix, stream);
 }
 
 int aws_huffman_amd_encode_plan_stored_size(
@@ -1490,14 +1537,8 @@ int aws_huffman_amd_encode_plan_stored_size(
         return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
     }
     uint64_t counts[2] = {0, 0};
-    ON_DEVICE(p->engine->device);
-    void *st = stream ? stream : p->engine->stream;
-    int err = p->n_items ? hufs_copy_d2h(counts, p->d_pack_summary + 2, sizeof(counts), st) : 0;
-    if (!err) {
-        err = hufs_stream_sync(st);
-    }
-    if (err) {
-        return raise_hip(err);
+    if (plan_read_words(p->engine->device, p->n_items ? p->d_pack_summary + 2 : NULL, counts, 2, stream ? stream : p->engine->stream)) {
+        return AWS_OP_ERR;
     }
     if (stored_items) {
         *stored_items = counts[0];
@@ -1518,14 +1559,8 @@ int aws_huffman_amd_encode_plan_packed_size(
         return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
     }
     uint64_t summary[2] = {0, 0};
-    ON_DEVICE(p->engine->device);
-    void *st = stream ? stream : p->engine->stream;
-    int err = p->n_items ? hufs_copy_d2h(summary, p->d_pack_summary, sizeof(summary), st) : 0;
-    if (!err) {
-        err = hufs_stream_sync(st);
-    }
-    if (err) {
-        return raise_hip(err);
+    if (plan_read_words(p->engine->device, p->n_items ? p->d_pack_summary : NULL, summary, 2, stream ? stream : p->engine->stream)) {
+        return AWS_OP_ERR;
     }
     if (total_bytes) {
         *total_bytes = summary[0];
@@ -1762,18 +1797,12 @@ static int dec_plan_reserve(struct aws_huffman_amd_decode_plan *p, size_t n_item
         dec_plan_release_device(p);
         const size_t ci = n_items ? n_items : 1, cc = n_chunks ? n_chunks : 1, cl = n_large ? n_large : 1;
         const size_t cr = n_runs ? n_runs : 1;
-        size_t total = 0;
-#define DEC_SIZE(name, bytes) (void)arena_cut(&total, (bytes));
-        DEC_PLAN_ARRAYS(DEC_SIZE, ci, cc, cl, cr, ns)
-#undef DEC_SIZE
-        p->d_arena = hufs_malloc(total);
-        if (!p->d_arena) {
+#define DEC_PART(name, bytes) {&p->name, (bytes)},
+        const struct arena_part parts[] = {DEC_PLAN_ARRAYS(DEC_PART, ci, cc, cl, cr, ns)};
+#undef DEC_PART
+        if (arena_alloc(&p->d_arena, ARENA_PARTS(parts))) {
             return 2;
         }
-        total = 0;
-#define DEC_PLACE(name, bytes) p->name = (void *)((uint8_t *)p->d_arena + arena_cut(&total, (bytes)));
-        DEC_PLAN_ARRAYS(DEC_PLACE, ci, cc, cl, cr, ns)
-#undef DEC_PLACE
         p->cap_items = ci;
         p->cap_chunks = cc;
         p->cap_large = cl;
@@ -2687,25 +2716,18 @@ static int dec_plan_reserve_packed(struct aws_huffman_amd_decode_plan *p, size_t
     if (p->d_packed_arena && n_items <= p->cap_packed_items && n_chunks <= p->cap_packed_chunks && n_tiles <= p->cap_pack_tiles) {
         return 0;
     }
-    hufs_free(p->d_packed_arena); /* (waits for what still reads it) */
-    p->d_packed_arena = NULL;
     p->cap_packed_items = p->cap_packed_chunks = p->cap_pack_tiles = 0;
     /* as many as the plan's own arrays: a reset within them allocates nothing */
     const size_t ci = n_items > p->cap_items ? n_items : p->cap_items;
     const size_t cc = n_chunks > p->cap_chunks ? n_chunks : p->cap_chunks;
-    size_t total = 0;
-    const size_t at_items = arena_cut(&total, ci * sizeof(struct hufd_dec_item));
-    const size_t at_chunks = arena_cut(&total, (cc ? cc : 1) * sizeof(struct hufd_chunk_rec));
-    const size_t at_sums = arena_cut(&total, 2 * n_tiles * sizeof(uint64_t));
-    const size_t at_summary = arena_cut(&total, 2 * sizeof(uint64_t));
-    p->d_packed_arena = hufs_malloc(total);
-    if (!p->d_packed_arena) {
+    const struct arena_part parts[] = {
+        {&p->d_packed_items, ci * sizeof(struct hufd_dec_item)},
+        {&p->d_packed_chunk_rec, (cc ? cc : 1) * sizeof(struct hufd_chunk_rec)},
+        {&p->d_pack_tile_sums, 2 * n_tiles * sizeof(uint64_t)},
+        {&p->d_pack_summary, 2 * sizeof(uint64_t)}};
+    if (arena_alloc(&p->d_packed_arena, ARENA_PARTS(parts))) {
         return 2;
     }
-    p->d_packed_items = (void *)((uint8_t *)p->d_packed_arena + at_items);
-    p->d_packed_chunk_rec = (void *)((uint8_t *)p->d_packed_arena + at_chunks);
-    p->d_pack_tile_sums = (void *)((uint8_t *)p->d_packed_arena + at_sums);
-    p->d_pack_summary = (void *)((uint8_t *)p->d_packed_arena + at_summary);
     p->cap_packed_items = ci;
     p->cap_packed_chunks = cc;
     p->cap_pack_tiles = n_tiles;
@@ -2793,14 +2815,8 @@ int aws_huffman_amd_decode_plan_packed_size(
         return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
     }
     uint64_t summary[2] = {0, 0};
-    ON_DEVICE(p->engine->device);
-    void *st = stream ? stream : p->engine->stream;
-    int err = p->n_items ? hufs_copy_d2h(summary, p->d_pack_summary, sizeof(summary), st) : 0;
-    if (!err) {
-        err = hufs_stream_sync(st);
-    }
-    if (err) {
-        return raise_hip(err);
+    if (plan_read_words(p->engine->device, p->n_items ? p->d_pack_summary : NULL, summary, 2, stream ? stream : p->engine->stream)) {
+        return AWS_OP_ERR;
     }
     if (total_symbols) {
         *total_symbols = summary[0];
@@ -2841,20 +2857,14 @@ static int dec_plan_reserve_stored(struct aws_huffman_amd_decode_plan *p, size_t
     if (p->d_stored_arena && n_items <= p->cap_stored_items && n_tiles <= p->cap_stored_tiles) {
         return 0;
     }
-    hufs_free(p->d_stored_arena); /* (waits for what still reads it) */
-    p->d_stored_arena = NULL;
     p->cap_stored_items = p->cap_stored_tiles = 0;
-    size_t total = 0;
-    const size_t at_rec = arena_cut(&total, 2 * n_items * sizeof(uint64_t));
-    const size_t at_first = arena_cut(&total, (n_items + 1) * sizeof(uint64_t));
-    const size_t at_sums = arena_cut(&total, 2 * n_tiles * sizeof(uint64_t));
-    p->d_stored_arena = hufs_malloc(total);
-    if (!p->d_stored_arena) {
+    const struct arena_part parts[] = {
+        {&p->d_stored_rec, 2 * n_items * sizeof(uint64_t)},
+        {&p->d_stored_tile_first, (n_items + 1) * sizeof(uint64_t)},
+        {&p->d_stored_tile_sums, 2 * n_tiles * sizeof(uint64_t)}};
+    if (arena_alloc(&p->d_stored_arena, ARENA_PARTS(parts))) {
         return 2;
     }
-    p->d_stored_rec = (void *)((uint8_t *)p->d_stored_arena + at_rec);
-    p->d_stored_tile_first = (void *)((uint8_t *)p->d_stored_arena + at_first);
-    p->d_stored_tile_sums = (void *)((uint8_t *)p->d_stored_arena + at_sums);
     p->cap_stored_items = n_items;
     p->cap_stored_tiles = n_tiles;
     return 0;
@@ -3028,46 +3038,31 @@ static int enc_plan_reserve_block_index(struct aws_huffman_amd_encode_plan *p, s
     if (p->d_block_index_arena && n_items <= p->cap_block_index_items && n_tiles <= p->cap_block_index_tiles) {
         return 0;
     }
-    hufs_free(p->d_block_index_arena); /* (waits for what still reads it) */
-    p->d_block_index_arena = NULL;
     p->cap_block_index_items = p->cap_block_index_tiles = 0;
     const size_t ci = n_items > p->cap_items ? n_items : p->cap_items; /* as many as the plan's own array: a reset within it allocates nothing */
-    size_t total = 0;
-    const size_t at_first = arena_cut(&total, (ci + 1) * sizeof(uint64_t));
-    const size_t at_sums = arena_cut(&total, 2 * n_tiles * sizeof(uint64_t));
-    const size_t at_summary = arena_cut(&total, sizeof(uint64_t));
-    p->d_block_index_arena = hufs_malloc(total);
-    if (!p->d_block_index_arena) {
+    const struct arena_part parts[] = {
+        {&p->d_block_index_tile_first, (ci + 1) * sizeof(uint64_t)},
+        {&p->d_block_index_tile_sums, 2 * n_tiles * sizeof(uint64_t)},
+        {&p->d_block_index_summary, sizeof(uint64_t)}};
+    if (arena_alloc(&p->d_block_index_arena, ARENA_PARTS(parts))) {
         return 2;
     }
-    p->d_block_index_tile_first = (void *)((uint8_t *)p->d_block_index_arena + at_first);
-    p->d_block_index_tile_sums = (void *)((uint8_t *)p->d_block_index_arena + at_sums);
-    p->d_block_index_summary = (void *)((uint8_t *)p->d_block_index_arena + at_summary);
     p->cap_block_index_items = ci;
     p->cap_block_index_tiles = n_tiles;
     return 0;
 }
 
 /* what a batch index asks of its arguments */
-static bool block_index_args_ok(
-    const struct aws_huffman_amd_encode_plan *p, const void *device_input, uint64_t block_symbols,
-    const struct aws_huffman_amd_item_blocks *device_directory, const uint64_t *device_index, uint64_t index_capacity,
-    const uint32_t *device_status) {
-    return p && device_directory && !((uintptr_t)device_directory & 7u) && !((uintptr_t)device_index & 7u) &&
-           !((uintptr_t)device_status & 3u) && (device_index == NULL) == (index_capacity == 0) && index_block_symbols_ok(block_symbols) &&
+static bool enc_plan_block_index_args_ok(
+    const struct aws_huffman_amd_encode_plan *p, const void *device_input, const struct enc_plan_index_args *ix) {
+    return p && ix->directory && !((uintptr_t)ix->directory & 7u) && !((uintptr_t)ix->index & 7u) && !((uintptr_t)ix->status & 3u) &&
+           (ix->index == NULL) == (ix->index_capacity == 0) && index_block_symbols_ok(ix->block_symbols) &&
            (!p->n_items || device_input);
 }
 
 /* the directory, the hot pass and the scan of a plan's batch index on `stream`: the arguments are good, the engine fitted */
 static int enc_plan_block_index_enqueue(
-    struct aws_huffman_amd_encode_plan *p,
-    const void *device_input,
-    uint64_t block_symbols,
-    struct aws_huffman_amd_item_blocks *device_directory,
-    uint64_t *device_index,
-    uint64_t index_capacity,
-    uint32_t *device_status,
-    void *stream) {
+    struct aws_huffman_amd_encode_plan *p, const void *device_input, const struct enc_plan_index_args *ix, void *stream) {
 
     struct aws_huffman_amd_engine *eng = p->engine;
     ON_DEVICE(eng->device);
@@ -3093,13 +3088,13 @@ static int enc_plan_block_index_enqueue(
     job.items = p->d_items;
     job.n_items = p->n_items;
     job.input = device_input;
-    job.block_symbols = block_symbols;
+    job.block_symbols = ix->block_symbols;
     job.wave_bytes = wave_bytes < HUFK_BATCH_WAVE_MAX_BYTES ? wave_bytes : HUFK_BATCH_WAVE_MAX_BYTES;
     job.index_tile_asked = __atomic_load_n(&s_index_tile_blocks, __ATOMIC_RELAXED);
-    job.directory = (uint64_t *)device_directory;
-    job.index = device_index;
-    job.capacity = index_capacity;
-    job.status = device_status;
+    job.directory = (uint64_t *)ix->directory;
+    job.index = ix->index;
+    job.capacity = ix->index_capacity;
+    job.status = ix->status;
     job.tile_first = p->d_block_index_tile_first;
     job.item_tile_sums = p->d_block_index_tile_sums;
     job.summary = p->d_block_index_summary;
@@ -3122,16 +3117,17 @@ int aws_huffman_amd_encode_plan_block_index(
     uint32_t *device_status,
     void *stream) {
 
+    const struct enc_plan_index_args ix = {block_symbols, device_directory, device_index, index_capacity, device_status};
     if (hufs_device_count() <= 0) {
         return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION); /* no GPU: there is no CPU path */
     }
-    if (!block_index_args_ok(p, device_input, block_symbols, device_directory, device_index, index_capacity, device_status)) {
+    if (!enc_plan_block_index_args_ok(p, device_input, &ix)) {
         return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
     }
     if (engine_never_fitted(p->engine)) {
         return aws_raise_error(AWS_ERROR_INVALID_STATE);
     }
-    if (enc_plan_block_index_enqueue(p, device_input, block_symbols, device_directory, device_index, index_capacity, device_status, stream)) {
+    if (enc_plan_block_index_enqueue(p, device_input, &ix, stream)) {
         return AWS_OP_ERR;
     }
     /* (the plan's records and scratch are read on this stream: whoever gets its arrays next waits, as for a launch) */
@@ -3140,140 +3136,25 @@ int aws_huffman_amd_encode_plan_block_index(
     return err ? raise_hip(err) : AWS_OP_SUCCESS;
 }
 
-/* ------------------------------------------------------------------ a packed launch that makes the index (huffman_amd_packed_index.h) */
-
-int aws_huffman_amd_encode_plan_launch_packed_indexed(
-    struct aws_huffman_amd_encode_plan *p,
-    const void *device_input,
-    void *device_output,
-    uint64_t output_capacity,
-    uint64_t *device_offsets,
-    uint32_t align,
-    uint64_t block_symbols,
-    struct aws_huffman_amd_item_blocks *device_directory,
-    uint64_t *device_index,
-    uint64_t index_capacity,
-    uint32_t *device_status,
-    void *stream) {
-
-    if (hufs_device_count() <= 0) {
-        return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION); /* no GPU: there is no CPU path */
-    }
-    if (!packed_launch_args_ok(p, device_output, output_capacity, device_offsets, align) || !device_index ||
-        !block_index_args_ok(p, device_input, block_symbols, device_directory, device_index, index_capacity, device_status)) {
-        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
-    }
-    if (engine_never_fitted(p->engine)) {
-        return aws_raise_error(AWS_ERROR_INVALID_STATE);
-    }
-    uint32_t tile_items = 0;
-    if (p->n_items && enc_plan_packed_tile_items(p, &tile_items)) {
-        return AWS_OP_ERR;
-    }
-    /* the index (its hot pass is the launch's length pass), the offsets and the second record array from it, the encode pass
-     * over that array: three stages on one stream, the symbols read twice */
-    if (enc_plan_block_index_enqueue(p, device_input, block_symbols, device_directory, device_index, index_capacity, device_status, stream)) {
-        return AWS_OP_ERR;
-    }
-    void *st = stream ? stream : p->engine->stream;
-    if (p->n_items == 0) {
-        if (enc_plan_launch_packed_empty(p, device_offsets, st)) {
-            return AWS_OP_ERR;
-        }
-        ON_DEVICE(p->engine->device);
-        const int err = plan_mark_done(&p->done_event, &p->done_on_engine_stream, p->engine, stream);
-        return err ? raise_hip(err) : AWS_OP_SUCCESS;
-    }
-    {
-        ON_DEVICE(p->engine->device);
-        const int e = hufk_pack_offsets_indexed(
-            p->d_items, p->n_items, tile_items, align, output_capacity, (const uint64_t *)device_directory, device_index, index_capacity,
-            p->d_pack_tile_sums, device_offsets, p->d_packed_items, p->d_pack_summary, st);
-        if (e) {
-            return raise_hip(e);
-        }
-    }
-    return enc_plan_launch_packed_items(p, device_input, device_output, stream);
-}
-
-/* ------------------------------------------------------------------ the same with items stored raw (huffman_amd_stored_index.h) */
-
-int aws_huffman_amd_encode_plan_launch_packed_stored_indexed(
-    struct aws_huffman_amd_encode_plan *p,
-    const void *device_input,
-    void *device_output,
-    uint64_t output_capacity,
-    uint64_t *device_offsets,
-    uint8_t *device_stored,
-    uint32_t align,
-    uint64_t block_symbols,
-    struct aws_huffman_amd_item_blocks *device_directory,
-    uint64_t *device_index,
-    uint64_t index_capacity,
-    uint32_t *device_status,
-    void *stream) {
-
-    if (hufs_device_count() <= 0) {
-        return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION); /* no GPU: there is no CPU path */
-    }
-    if (!packed_launch_args_ok(p, device_output, output_capacity, device_offsets, align) || !device_stored || !device_index ||
-        !block_index_args_ok(p, device_input, block_symbols, device_directory, device_index, index_capacity, device_status)) {
-        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
-    }
-    if (engine_never_fitted(p->engine)) {
-        return aws_raise_error(AWS_ERROR_INVALID_STATE);
-    }
-    uint32_t tile_items = 0;
-    if (p->n_items && enc_plan_packed_tile_items(p, &tile_items)) {
-        return AWS_OP_ERR;
-    }
-    /* the stages of an indexed launch with the scan that decides -- the coded lengths out of the index, flags, offsets, no room
-     * for a stored item in the second record array --, then the copy of the stored items behind the encode pass: one stream,
-     * the symbols read twice and the stored ones once more */
-    if (enc_plan_block_index_enqueue(p, device_input, block_symbols, device_directory, device_index, index_capacity, device_status, stream)) {
-        return AWS_OP_ERR;
-    }
-    void *st = stream ? stream : p->engine->stream;
-    if (p->n_items == 0) {
-        if (enc_plan_launch_packed_empty(p, device_offsets, st)) {
-            return AWS_OP_ERR;
-        }
-        p->stored = true;
-        ON_DEVICE(p->engine->device);
-        const int err = plan_mark_done(&p->done_event, &p->done_on_engine_stream, p->engine, stream);
-        return err ? raise_hip(err) : AWS_OP_SUCCESS;
-    }
-    {
-        ON_DEVICE(p->engine->device);
-        const int e = hufk_pack_offsets_stored_indexed(
-            p->d_items, p->n_items, tile_items, align, output_capacity, (const uint64_t *)device_directory, device_index, index_capacity,
-            p->d_pack_tile_sums, device_offsets, p->d_packed_items, p->d_pack_summary, device_stored, st);
-        if (e) {
-            return raise_hip(e);
-        }
-    }
-    if (enc_plan_launch_packed_items(p, device_input, device_output, stream)) {
-        return AWS_OP_ERR;
-    }
-    return enc_plan_launch_stored_copy(p, device_input, device_output, output_capacity, device_offsets, device_stored, stream);
-}
-
 int aws_huffman_amd_encode_plan_block_index_size(struct aws_huffman_amd_encode_plan *p, uint64_t *entries, void *stream) {
     if (!p || !entries || !p->block_indexed) {
         return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
     }
     uint64_t blocks = 0;
-    ON_DEVICE(p->engine->device);
-    void *st = stream ? stream : p->engine->stream;
-    int err = hufs_copy_d2h(&blocks, p->d_block_index_summary, sizeof(blocks), st);
-    if (!err) {
-        err = hufs_stream_sync(st);
-    }
-    if (err) {
-        return raise_hip(err);
+    if (plan_read_words(p->engine->device, p->d_block_index_summary, &blocks, 1, stream ? stream : p->engine->stream)) {
+        return AWS_OP_ERR;
     }
     *entries = blocks + 1;
     return AWS_OP_SUCCESS;
+}
+
+/* a reset of ranges whose arguments are refused: a plan without items, as a refused range leaves it, and INVALID_ARGUMENT */
+static int dec_plan_refuse(struct aws_huffman_amd_decode_plan *p, uint32_t kind, void *stream) {
+    struct hufd_item_source src;
+    memset(&src, 0, sizeof(src));
+    src.kind = kind;
+    const int rc = dec_plan_fill_on_device(p, &src, 0, stream);
+    return rc ? rc : aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
 }
 
 int aws_huffman_amd_decode_plan_reset_block_ranges(
@@ -3293,14 +3174,13 @@ int aws_huffman_amd_decode_plan_reset_block_ranges(
     if (!p) {
         return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
     }
+    if (!device_index || ((uintptr_t)device_index & 7u) || (!device_ranges && range_count) || ((uintptr_t)device_ranges & 7u) ||
+        !index_block_symbols_ok(block_symbols)) {
+        return dec_plan_refuse(p, HUFD_ITEMS_BLOCK_RANGES, stream);
+    }
     struct hufd_item_source src;
     memset(&src, 0, sizeof(src));
     src.kind = HUFD_ITEMS_BLOCK_RANGES;
-    if (!device_index || ((uintptr_t)device_index & 7u) || (!device_ranges && range_count) || ((uintptr_t)device_ranges & 7u) ||
-        !index_block_symbols_ok(block_symbols)) {
-        const int rc = dec_plan_fill_on_device(p, &src, 0, stream); /* (a plan without items, as a refused range leaves it) */
-        return rc ? rc : aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
-    }
     /* the planner reads the ranges and the two index entries at each range's ends where it reads any item's record: a
      * refused range is its statistics pass's `invalid`, which comes back with the totals */
     src.block_index = device_index;
@@ -3372,16 +3252,15 @@ int aws_huffman_amd_decode_plan_reset_stored_item_block_ranges(
     if (!p) {
         return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
     }
-    struct hufd_item_source src;
-    memset(&src, 0, sizeof(src));
-    src.kind = HUFD_ITEMS_ITEM_BLOCK_RANGES;
     if (!device_directory || ((uintptr_t)device_directory & 7u) || !device_index || ((uintptr_t)device_index & 7u) || index_entries == 0 ||
         item_count >= 0xFFFFFFFFull || !device_encoded_offsets || ((uintptr_t)device_encoded_offsets & 7u) ||
         ((uintptr_t)device_encoded_lengths & 7u) || (!device_ranges && range_count) || ((uintptr_t)device_ranges & 7u) ||
         !index_block_symbols_ok(block_symbols)) {
-        const int rc = dec_plan_fill_on_device(p, &src, 0, stream); /* (a plan without items, as a refused range leaves it) */
-        return rc ? rc : aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+        return dec_plan_refuse(p, HUFD_ITEMS_ITEM_BLOCK_RANGES, stream);
     }
+    struct hufd_item_source src;
+    memset(&src, 0, sizeof(src));
+    src.kind = HUFD_ITEMS_ITEM_BLOCK_RANGES;
     /* the planner reads a range, its item's two directory records, place and three index entries where it reads any item's
      * record: a refused range is its statistics pass's `invalid`, which comes back with the totals */
     src.item_block_ranges = (const struct hufd_item_block_range *)device_ranges;
@@ -3419,33 +3298,49 @@ void aws_huffman_amd_testing_set_locate_lone_symbols(uint32_t symbols) {
     __atomic_store_n(&s_locate_lone_symbols, symbols, __ATOMIC_RELAXED);
 }
 
-/* the locate launches (and the memset that clears the status in front of them) on `st`: nothing waited for */
-static int locate_enqueue(
-    struct aws_huffman_amd_engine *eng, const void *encoded, uint64_t encoded_length, const uint64_t *index, uint64_t length,
-    uint64_t block_symbols, const uint64_t *symbols, const struct hufd_symbol_range *ranges, uint64_t count, uint64_t *bits,
-    uint32_t *status, void *st) {
-    struct hufd_locate job;
-    memset(&job, 0, sizeof(job));
-    job.encoded = encoded;
-    job.encoded_length = encoded_length;
-    job.index = index;
-    job.length = length;
-    job.block_symbols = block_symbols;
-    job.n_blocks = (length + block_symbols - 1) / block_symbols;
-    job.symbols = symbols;
-    job.ranges = ranges;
-    job.count = count;
-    job.bits = bits;
-    job.status = status;
+/* a job of positions in one indexed stream; the caller adds what is located (symbols or ranges, count, bits, status) */
+static void locate_stream_job(
+    struct hufd_locate *job, const void *encoded, uint64_t encoded_length, const uint64_t *index, uint64_t length, uint64_t block_symbols) {
+    memset(job, 0, sizeof(*job));
+    job->encoded = encoded;
+    job->encoded_length = encoded_length;
+    job->index = index;
+    job->length = length;
+    job->block_symbols = block_symbols;
+    job->n_blocks = (length + block_symbols - 1) / block_symbols;
+}
+
+/* the locate launches of a job (and the memset that clears its status in front of them) on `st`: nothing waited for */
+static int locate_launch(const struct aws_huffman_amd_engine *eng, struct hufd_locate *job, void *st) {
     const uint32_t asked = __atomic_load_n(&s_locate_lone_symbols, __ATOMIC_RELAXED);
-    job.lone_symbols = asked ? asked : LOCATE_LONE_SYMBOLS;
+    job->lone_symbols = asked ? asked : LOCATE_LONE_SYMBOLS;
     /* (a coder of one code length needs no walk; blocks no longer than the limit have no position behind it) */
-    const uint32_t walks_coop = !eng->tables.fixed_bits && (uint64_t)job.lone_symbols + 1 < block_symbols;
-    int err = status ? hufs_memset(status, 0, sizeof(uint32_t), st) : 0;
-    if (!err && count) {
-        err = hufk_locate_symbols(&eng->tables, &job, walks_coop, st);
+    const uint32_t walks_coop = !eng->tables.fixed_bits && (uint64_t)job->lone_symbols + 1 < job->block_symbols;
+    int err = job->status ? hufs_memset(job->status, 0, sizeof(uint32_t), st) : 0;
+    if (!err && job->count) {
+        err = hufk_locate_symbols(&eng->tables, job, walks_coop, st);
     }
     return err;
+}
+
+/* Both ends of every range of a reset of symbol ranges (job->ranges or job->item_ranges), located on the caller's stream into
+ * words the plan owns (two a range: grown, never shrunk), in front of the planner's passes, which read a range and its two bits
+ * where they read any item's record: a refused range (an end that was not found among them) is the statistics pass's `invalid`,
+ * which comes back with the totals. */
+static int dec_plan_locate_range_ends(struct aws_huffman_amd_decode_plan *p, struct hufd_locate *job, size_t range_count, void *stream) {
+    ON_DEVICE(p->engine->device);
+    if (2 * range_count > p->cap_range_bits) {
+        hufs_free(p->d_range_bits);
+        p->d_range_bits = hufs_malloc(2 * range_count * sizeof(uint64_t));
+        p->cap_range_bits = p->d_range_bits ? 2 * range_count : 0;
+    }
+    if (!p->d_range_bits) {
+        return raise_hip(2);
+    }
+    job->count = 2 * (uint64_t)range_count;
+    job->bits = p->d_range_bits;
+    const int err = locate_launch(p->engine, job, stream ? stream : p->engine->stream);
+    return err ? raise_hip(err) : AWS_OP_SUCCESS;
 }
 
 int aws_huffman_amd_locate_symbols(
@@ -3478,10 +3373,14 @@ int aws_huffman_amd_locate_symbols(
     if (engine_never_fitted(eng)) {
         return aws_raise_error(AWS_ERROR_INVALID_STATE);
     }
+    struct hufd_locate job;
+    locate_stream_job(&job, device_encoded, encoded_length, device_index, length, block_symbols);
+    job.symbols = device_symbols;
+    job.count = count;
+    job.bits = device_bits;
+    job.status = device_status;
     ON_DEVICE(eng->device);
-    const int err = locate_enqueue(
-        eng, device_encoded, encoded_length, device_index, length, block_symbols, device_symbols, NULL, count, device_bits,
-        device_status, stream ? stream : eng->stream);
+    const int err = locate_launch(eng, &job, stream ? stream : eng->stream);
     return err ? raise_hip(err) : AWS_OP_SUCCESS;
 }
 
@@ -3507,39 +3406,25 @@ int aws_huffman_amd_decode_plan_reset_symbol_ranges(
     if (engine_never_fitted(eng)) {
         return aws_raise_error(AWS_ERROR_INVALID_STATE);
     }
-    struct hufd_item_source src;
-    memset(&src, 0, sizeof(src));
-    src.kind = HUFD_ITEMS_SYMBOL_RANGES;
     if (!device_index || ((uintptr_t)device_index & 7u) || (!device_ranges && range_count) || ((uintptr_t)device_ranges & 7u) ||
         (!device_input && range_count) || !index_block_symbols_ok(block_symbols) ||
         (length + block_symbols - 1) / block_symbols > 0xFFFFFFFFull || range_count >= 0xFFFFFFFFull) {
-        const int rc = dec_plan_fill_on_device(p, &src, 0, stream); /* (a plan without items, as a refused range leaves it) */
-        return rc ? rc : aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+        return dec_plan_refuse(p, HUFD_ITEMS_SYMBOL_RANGES, stream);
     }
     if (!eng->can_decode) {
         return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION);
     }
-    /* both ends of every range are located on the caller's stream, into words the plan owns, in front of the planner's
-     * passes, which read a range and its two bits where they read any item's record: a refused range (an end that was
-     * not found among them) is the statistics pass's `invalid`, which comes back with the totals */
     if (range_count) {
-        ON_DEVICE(eng->device);
-        if (2 * range_count > p->cap_range_bits) {
-            hufs_free(p->d_range_bits);
-            p->d_range_bits = hufs_malloc(2 * range_count * sizeof(uint64_t));
-            p->cap_range_bits = p->d_range_bits ? 2 * range_count : 0;
-        }
-        if (!p->d_range_bits) {
-            return raise_hip(2);
-        }
-        const int err = locate_enqueue(
-            eng, (const uint8_t *)device_input + encoded_offset, encoded_length, device_index, length, block_symbols, NULL,
-            (const struct hufd_symbol_range *)device_ranges, 2 * (uint64_t)range_count, p->d_range_bits, NULL,
-            stream ? stream : eng->stream);
-        if (err) {
-            return raise_hip(err);
+        struct hufd_locate job;
+        locate_stream_job(&job, (const uint8_t *)device_input + encoded_offset, encoded_length, device_index, length, block_symbols);
+        job.ranges = (const struct hufd_symbol_range *)device_ranges;
+        if (dec_plan_locate_range_ends(p, &job, range_count, stream)) {
+            return AWS_OP_ERR;
         }
     }
+    struct hufd_item_source src;
+    memset(&src, 0, sizeof(src));
+    src.kind = HUFD_ITEMS_SYMBOL_RANGES;
     src.symbol_ranges = (const struct hufd_symbol_range *)device_ranges;
     src.located_bits = p->d_range_bits;
     src.stream_symbols = length;
@@ -3571,36 +3456,19 @@ static bool batch_place_ok(const struct batch_place *b) {
            index_block_symbols_ok(b->block_symbols);
 }
 
-/* locate_enqueue for positions addressed by item: items[i] / symbols[i], or the ends of ranges */
-static int locate_items_enqueue(
-    struct aws_huffman_amd_engine *eng, const struct batch_place *b, const uint64_t *items, const uint64_t *symbols,
-    const struct hufd_item_symbol_range *ranges, uint64_t count, uint64_t *bits, uint32_t *status, void *st) {
-    struct hufd_locate job;
-    memset(&job, 0, sizeof(job));
-    job.encoded = b->encoded;
-    job.encoded_length = b->encoded_length;
-    job.index = b->index;
-    job.block_symbols = b->block_symbols;
-    job.symbols = symbols;
-    job.items = items;
-    job.item_ranges = ranges;
-    job.directory = b->directory;
-    job.offsets = b->offsets;
-    job.lengths = b->lengths;
-    job.stored = b->stored;
-    job.item_count = b->item_count;
-    job.index_entries = b->index_entries;
-    job.count = count;
-    job.bits = bits;
-    job.status = status;
-    const uint32_t asked = __atomic_load_n(&s_locate_lone_symbols, __ATOMIC_RELAXED);
-    job.lone_symbols = asked ? asked : LOCATE_LONE_SYMBOLS;
-    const uint32_t walks_coop = !eng->tables.fixed_bits && (uint64_t)job.lone_symbols + 1 < b->block_symbols;
-    int err = status ? hufs_memset(status, 0, sizeof(uint32_t), st) : 0;
-    if (!err && count) {
-        err = hufk_locate_symbols(&eng->tables, &job, walks_coop, st);
-    }
-    return err;
+/* as locate_stream_job, for positions addressed by item: items[i] / symbols[i], or the ends of item_ranges */
+static void locate_batch_job(struct hufd_locate *job, const struct batch_place *b) {
+    memset(job, 0, sizeof(*job));
+    job->encoded = b->encoded;
+    job->encoded_length = b->encoded_length;
+    job->index = b->index;
+    job->block_symbols = b->block_symbols;
+    job->directory = b->directory;
+    job->offsets = b->offsets;
+    job->lengths = b->lengths;
+    job->stored = b->stored;
+    job->item_count = b->item_count;
+    job->index_entries = b->index_entries;
 }
 
 int aws_huffman_amd_locate_item_symbols(
@@ -3661,9 +3529,15 @@ int aws_huffman_amd_locate_stored_item_symbols(
     if (engine_never_fitted(eng)) {
         return aws_raise_error(AWS_ERROR_INVALID_STATE);
     }
+    struct hufd_locate job;
+    locate_batch_job(&job, &place);
+    job.items = device_items;
+    job.symbols = device_symbols;
+    job.count = count;
+    job.bits = device_bits;
+    job.status = device_status;
     ON_DEVICE(eng->device);
-    const int err = locate_items_enqueue(
-        eng, &place, device_items, device_symbols, NULL, count, device_bits, device_status, stream ? stream : eng->stream);
+    const int err = locate_launch(eng, &job, stream ? stream : eng->stream);
     return err ? raise_hip(err) : AWS_OP_SUCCESS;
 }
 
@@ -3714,39 +3588,27 @@ int aws_huffman_amd_decode_plan_reset_stored_item_symbol_ranges(
     if (engine_never_fitted(eng)) {
         return aws_raise_error(AWS_ERROR_INVALID_STATE);
     }
-    struct hufd_item_source src;
-    memset(&src, 0, sizeof(src));
-    src.kind = HUFD_ITEMS_ITEM_SYMBOL_RANGES;
     const struct batch_place place = {(const uint8_t *)device_input + encoded_offset, encoded_length, (const uint64_t *)device_directory,
                                       device_index, device_encoded_offsets, device_encoded_lengths, index_entries, item_count,
                                       block_symbols, device_stored};
     if (!batch_place_ok(&place) || (!device_ranges && range_count) || ((uintptr_t)device_ranges & 7u) || (!device_input && range_count) ||
         range_count >= 0xFFFFFFFFull) {
-        const int rc = dec_plan_fill_on_device(p, &src, 0, stream); /* (a plan without items, as a refused range leaves it) */
-        return rc ? rc : aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+        return dec_plan_refuse(p, HUFD_ITEMS_ITEM_SYMBOL_RANGES, stream);
     }
     if (!eng->can_decode) {
         return aws_raise_error(AWS_ERROR_UNSUPPORTED_OPERATION);
     }
-    /* as aws_huffman_amd_decode_plan_reset_symbol_ranges: both ends of every range located on the caller's stream into words
-     * the plan owns, in front of the planner's passes; an end that was not found is the statistics pass's `invalid` */
-    if (range_count) {
-        ON_DEVICE(eng->device);
-        if (2 * range_count > p->cap_range_bits) {
-            hufs_free(p->d_range_bits);
-            p->d_range_bits = hufs_malloc(2 * range_count * sizeof(uint64_t));
-            p->cap_range_bits = p->d_range_bits ? 2 * range_count : 0;
-        }
-        if (!p->d_range_bits) {
-            return raise_hip(2);
-        }
-        const int err = locate_items_enqueue(
-            eng, &place, NULL, NULL, (const struct hufd_item_symbol_range *)device_ranges, 2 * (uint64_t)range_count, p->d_range_bits,
-            NULL, stream ? stream : eng->stream);
-        if (err) {
-            return raise_hip(err);
+    if (range_count) { /* (as aws_huffman_amd_decode_plan_reset_symbol_ranges) */
+        struct hufd_locate job;
+        locate_batch_job(&job, &place);
+        job.item_ranges = (const struct hufd_item_symbol_range *)device_ranges;
+        if (dec_plan_locate_range_ends(p, &job, range_count, stream)) {
+            return AWS_OP_ERR;
         }
     }
+    struct hufd_item_source src;
+    memset(&src, 0, sizeof(src));
+    src.kind = HUFD_ITEMS_ITEM_SYMBOL_RANGES;
     src.item_symbol_ranges = (const struct hufd_item_symbol_range *)device_ranges;
     src.located_bits = p->d_range_bits;
     src.batch_directory = (const uint64_t *)device_directory;
@@ -3950,27 +3812,24 @@ int aws_huffman_amd_decode_plan_from_encode(
 
 /* ------------------------------------------------------------------ one-item helpers for the host-pointer API */
 
-static int one_shot_reserve(struct aws_huffman_amd_engine *eng, size_t in_bytes, size_t out_bytes) {
-    ON_DEVICE(eng->device);
-    if (in_bytes > eng->one_in_cap) {
-        hufs_free(eng->one_in);
-        eng->one_in_cap = in_bytes + in_bytes / 4 + 4096;
-        eng->one_in = hufs_malloc(eng->one_in_cap);
-        if (!eng->one_in) {
-            eng->one_in_cap = 0;
-            return aws_raise_error(AWS_ERROR_OOM);
-        }
-    }
-    if (out_bytes > eng->one_out_cap) {
-        hufs_free(eng->one_out);
-        eng->one_out_cap = out_bytes + out_bytes / 4 + 4096;
-        eng->one_out = hufs_malloc(eng->one_out_cap);
-        if (!eng->one_out) {
-            eng->one_out_cap = 0;
+/* one of the engine's two staging buffers, grown by a quarter more than asked */
+static int one_shot_grow(void **buffer, size_t *cap, size_t bytes) {
+    if (bytes > *cap) {
+        *cap = bytes + bytes / 4 + 4096;
+        const struct arena_part whole = {buffer, *cap};
+        if (arena_alloc(buffer, &whole, 1)) {
+            *cap = 0;
             return aws_raise_error(AWS_ERROR_OOM);
         }
     }
     return AWS_OP_SUCCESS;
+}
+
+static int one_shot_reserve(struct aws_huffman_amd_engine *eng, size_t in_bytes, size_t out_bytes) {
+    ON_DEVICE(eng->device);
+    return one_shot_grow(&eng->one_in, &eng->one_in_cap, in_bytes) || one_shot_grow(&eng->one_out, &eng->one_out_cap, out_bytes)
+               ? AWS_OP_ERR
+               : AWS_OP_SUCCESS;
 }
 
 /*
