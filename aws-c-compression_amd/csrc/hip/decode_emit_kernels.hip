@@ -346,7 +346,6 @@ __global__ __launch_bounds__(kEmitThreads, 4) void dec_emit_kernel(
  */
 constexpr u32 kEmitChains = 2; /* quarters of sub-chunks a thread walks side by side: two independent chains per lane hide the table latency */
 constexpr u32 kEmitFastThreads = kEmitThreads / kEmitChains;
-constexpr u32 kEmitHalf = HUFD_DEC_LANES / kEmitChains;
 
 template <u32 LB>
 struct emit_shared {
@@ -387,13 +386,13 @@ __device__ __forceinline__ void dec_emit_fast_chunk(
 
     emit_shared<LB> &sh = *reinterpret_cast<emit_shared<LB> *>(dyn_lds);
     const u32 t = threadIdx.x;
-    /* my quarter of two sub-chunks.  In a chunk that holds the end of a stream only the first lanes have data: there a
-     * thread takes two NEIGHBOURING sub-chunks and the threads are numbered sub-chunks first, so that the idle ones fill
-     * whole waves, which then skip the walk (the kernel is bound by instruction issue: an idle wave's slots go to the
-     * other workgroups of the CU) */
-    const u32 q = TAIL ? t % kQuarters : t / kEmitHalf;
-    const u32 lanes[kEmitChains] = {TAIL ? 2 * (t / kQuarters) : t % kEmitHalf,
-                                    TAIL ? 2 * (t / kQuarters) + 1 : t % kEmitHalf + kEmitHalf};
+    /* my quarter of two NEIGHBOURING sub-chunks, the threads numbered quarter first: four neighbouring threads take the four
+     * quarters of one sub-chunk, which is one 128-byte line of the stream, so a wave's load touches 16 lines and every line
+     * is asked for by one wave only (sub-chunk first, 64 lanes stood on 64 lines, each asked for by four waves).  In a chunk
+     * that holds the end of a stream only the first lanes have data: there the idle threads so fill whole waves, which then
+     * skip the walk (the kernel is bound by instruction issue: an idle wave's slots go to the other workgroups of the CU) */
+    const u32 q = t % kQuarters;
+    const u32 lanes[kEmitChains] = {2 * (t / kQuarters), 2 * (t / kQuarters) + 1};
     /* the table entries this thread will put into LDS: asked for first, they depend on nothing */
     /* (TAIL with a 10-bit table: the workgroup may be launched with fewer threads than 512 -- 256 at least --, see the launch) */
     constexpr bool kNarrowBlock = TAIL && LB == 10;
@@ -497,25 +496,13 @@ __device__ __forceinline__ void dec_emit_fast_chunk(
         return;
     }
     /* where every sub-chunk's symbols go: lane 0's count follows from the chunk's total */
-    u32 incl[kEmitChains] = {0, 0};
-    const u32 wl = t & (kWave - 1), half_wave = (t / kWave) & (kEmitHalf / kWave - 1);
-    u32 own_cnt = 0; /* TAIL: thread t < 256 does this for sub-chunk t, whoever walks it */
-    if (TAIL) {
-        if (t < HUFD_DEC_LANES) {
-            /* (the lanes behind the stream's last two sub-chunks hold nothing; dec_sync_pack does not even write their records) */
-            own_cnt = t < n_full + 2 ? lane_count[(u64)c * HUFD_DEC_LANES + t] : 0u;
-            incl[0] = wave_inclusive_sum(t ? own_cnt : 0u, wl);
-            if (wl == kWave - 1) {
-                sh.wave_tot[t / kWave] = incl[0];
-            }
-        }
-    } else if (q == 0) {
-#pragma unroll
-        for (u32 ch = 0; ch < kEmitChains; ++ch) {
-            incl[ch] = wave_inclusive_sum(lanes[ch] ? cnt[ch] : 0u, wl);
-            if (wl == kWave - 1) {
-                sh.wave_tot[ch * (kEmitHalf / kWave) + half_wave] = incl[ch]; /* = lanes[ch] / 64 */
-            }
+    u32 incl = 0, own_cnt = 0; /* thread t < 256 does this for sub-chunk t, whoever walks it */
+    if (t < HUFD_DEC_LANES) {
+        /* (TAIL: the lanes behind the stream's last two sub-chunks hold nothing; dec_sync_pack does not even write their records) */
+        own_cnt = t < n_full + 2 ? lane_count[(u64)c * HUFD_DEC_LANES + t] : 0u;
+        incl = wave_inclusive_sum(t ? own_cnt : 0u, t & (kWave - 1));
+        if ((t & (kWave - 1)) == kWave - 1) {
+            sh.wave_tot[t / kWave] = incl;
         }
     }
     __syncthreads();
@@ -525,25 +512,13 @@ __device__ __forceinline__ void dec_emit_fast_chunk(
         rest += sh.wave_tot[wv];
     }
     const u32 first_count = chunk_symbols - rest; /* sub-chunk 0, entered in state s0 */
-    if (TAIL) {
-        if (t < HUFD_DEC_LANES) {
-            u32 before = 0;
+    if (t < HUFD_DEC_LANES) {
+        u32 before = 0;
 #pragma unroll
-            for (u32 wv = 0; wv < HUFD_DEC_LANES / kWave; ++wv) {
-                before += wv < t / kWave ? sh.wave_tot[wv] : 0u;
-            }
-            sh.lane_base[t] = t ? first_count + before + incl[0] - own_cnt : 0u;
+        for (u32 wv = 0; wv < HUFD_DEC_LANES / kWave; ++wv) {
+            before += wv < t / kWave ? sh.wave_tot[wv] : 0u;
         }
-    } else if (q == 0) {
-#pragma unroll
-        for (u32 ch = 0; ch < kEmitChains; ++ch) {
-            u32 before = 0;
-#pragma unroll
-            for (u32 wv = 0; wv < HUFD_DEC_LANES / kWave; ++wv) {
-                before += wv < lanes[ch] / kWave ? sh.wave_tot[wv] : 0u;
-            }
-            sh.lane_base[lanes[ch]] = lanes[ch] ? first_count + before + incl[ch] - cnt[ch] : 0u;
-        }
+        sh.lane_base[t] = t ? first_count + before + incl - own_cnt : 0u;
     }
     __syncthreads();
     HUFD_STAMP(1, 1);
