@@ -24,6 +24,50 @@ constexpr u32 kEmitThreads = HUFD_DEC_LANES * kQuarters;
 constexpr u32 kExitStop = 15, kExitNoRef = 14;        /* top nibble of the merged-state row (states are < 13) */
 constexpr u8 kRegularFew = 4; /* chunk_regular between dec_sync_few and dec_sync_true (0: the long way, 1: regular, 2: regular up to the end of its stream, 3: a thread's work) */
 
+/*
+ * A sub-chunk's record (hufd_lane_rec) as the four words it travels in: x = cp[0] | cp[1] << 16, y = cp[2] | merged << 16,
+ * z = count, w = 0.  Every kernel loads and stores records through lane_rec_load / lane_rec_store (lane_rec_count and
+ * lane_rec_merged where one field of a record is all a thread wants); none indexes the array by hand.
+ */
+static_assert(sizeof(hufd_lane_rec) == 16 && alignof(hufd_lane_rec) == 16, "a record is one 16-byte load or store");
+static_assert(kQuarters - 1 == 3 && kCpRows == kQuarters, "three checkpoints and the merged word a record");
+
+__device__ __forceinline__ uint4 lane_rec_load(const hufd_lane_rec *lane_rec, u32 c, u32 lane) {
+    return *reinterpret_cast<const uint4 *>(lane_rec + (u64)c * HUFD_DEC_LANES + lane);
+}
+__device__ __forceinline__ void lane_rec_store(hufd_lane_rec *lane_rec, u32 c, u32 lane, const uint4 &v) {
+    *reinterpret_cast<uint4 *>(lane_rec + (u64)c * HUFD_DEC_LANES + lane) = v;
+}
+/* (the low 16 bits of each value: what a store to a u16 kept) */
+__device__ __forceinline__ uint4 lane_rec_pack(u32 cp0, u32 cp1, u32 cp2, u32 merged, u32 count) {
+    uint4 v;
+    v.x = (cp0 & 0xFFFFu) | (cp1 << 16);
+    v.y = (cp2 & 0xFFFFu) | (merged << 16);
+    v.z = count & 0xFFFFu;
+    v.w = 0;
+    return v;
+}
+/* a sub-chunk the true path never gets to, as far as its writer knows: no checkpoint, no symbol, a stop for an exit */
+__device__ __forceinline__ uint4 lane_rec_unreached() {
+    return lane_rec_pack(0, 0, 0, kExitStop << 12, 0);
+}
+__device__ __forceinline__ u32 lane_rec_cp(const uint4 &v, u32 qq) { /* checkpoint qq (0 .. 2): the walk where it enters quarter qq + 1 */
+    return qq == 0 ? v.x & 0xFFFFu : (qq == 1 ? v.x >> 16 : v.y & 0xFFFFu);
+}
+__device__ __forceinline__ u32 lane_rec_merged(const uint4 &v) {
+    return v.y >> 16;
+}
+__device__ __forceinline__ u32 lane_rec_count(const uint4 &v) {
+    return v.z & 0xFFFFu;
+}
+/* one field of a record by itself: a 2-byte load */
+__device__ __forceinline__ u32 lane_rec_merged(const hufd_lane_rec *lane_rec, u32 c, u32 lane) {
+    return lane_rec[(u64)c * HUFD_DEC_LANES + lane].merged;
+}
+__device__ __forceinline__ u32 lane_rec_count(const hufd_lane_rec *lane_rec, u32 c, u32 lane) {
+    return lane_rec[(u64)c * HUFD_DEC_LANES + lane].count;
+}
+
 /* narrow transfer-function entry (per sub-chunk): [15] stop, [14:11] exit state, [10:0] symbols */
 __device__ __forceinline__ u16 fn_pack(bool stop, u32 exit_state, u32 count) {
     return (u16)((stop ? 0x8000u : 0u) | (exit_state << 11) | count);

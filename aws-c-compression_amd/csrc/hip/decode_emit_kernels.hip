@@ -25,8 +25,7 @@ __device__ __forceinline__ void dec_emit_chunk(
     const u8 *d_in,
     u8 *d_out,
     const u16 *fn_tab,
-    const u16 *cp_tab,
-    const u16 *lane_count_tab, /* regular chunks: the symbol counts of lanes >= 1 are here, not in fn_tab */
+    const hufd_lane_rec *lane_rec,
     const u8 *chunk_regular,
     const u32 *chunk_entry,
     const u64 *chunk_base,
@@ -61,7 +60,10 @@ __device__ __forceinline__ void dec_emit_chunk(
 
     HUFD_STAMP(1, 0);
     /* the two small tables first, so that their latency hides behind the chunk itself */
-    const u16 my_cp = cp_tab[(u64)c * kCpRows * HUFD_DEC_LANES + t]; /* kCpRows * lanes == threads */
+    uint4 my_rec = lane_rec_unreached(); /* thread t < lanes: sub-chunk t's record, whose values go into LDS row by row */
+    if (t < HUFD_DEC_LANES) {
+        my_rec = lane_rec_load(lane_rec, c, t);
+    }
     u16 my_fn[(HUFD_DEC_MAX_STATES * HUFD_DEC_LANES + kEmitThreads - 1) / kEmitThreads];
 #pragma unroll
     for (u32 j = 0; j < sizeof(my_fn) / sizeof(my_fn[0]); ++j) {
@@ -70,7 +72,13 @@ __device__ __forceinline__ void dec_emit_chunk(
     }
     chunk_load<kEmitThreads>(timg, d_in + it.in_off + chunk_off, valid);
     lut_load<kEmitThreads>(lut, tb);
-    cpt[t] = my_cp;
+    if (t < HUFD_DEC_LANES) {
+#pragma unroll
+        for (u32 qq = 0; qq + 1 < kQuarters; ++qq) {
+            cpt[qq * HUFD_DEC_LANES + t] = (u16)lane_rec_cp(my_rec, qq);
+        }
+        cpt[(kQuarters - 1) * HUFD_DEC_LANES + t] = (u16)lane_rec_merged(my_rec);
+    }
 #pragma unroll
     for (u32 j = 0; j < sizeof(my_fn) / sizeof(my_fn[0]); ++j) {
         const u32 i = t + j * kEmitThreads;
@@ -116,7 +124,7 @@ __device__ __forceinline__ void dec_emit_chunk(
         }
         lane_state = (fits && lane_reached) ? lane_state : 0;
         lane_count = !lane_reached ? 0u
-                     : (t != 0 && chunk_regular[c] != 0) ? (u32)lane_count_tab[(u64)c * HUFD_DEC_LANES + t]
+                     : (t != 0 && chunk_regular[c] != 0) ? lane_rec_count(my_rec)
                                                          : (u32)(ftab[lane_state * HUFD_DEC_LANES + t] & 0x7FFu);
         lane_incl = wave_inclusive_sum(lane_count, t & (kWave - 1));
         if ((t & (kWave - 1)) == kWave - 1) {
@@ -302,8 +310,7 @@ __global__ __launch_bounds__(kEmitThreads, 4) void dec_emit_kernel(
     const u8 *d_in,
     u8 *d_out,
     const u16 *fn_tab,
-    const u16 *cp_tab,
-    const u16 *lane_count_tab,
+    const hufd_lane_rec *lane_rec,
     const u8 *chunk_regular,
     const u32 *chunk_entry,
     const u64 *chunk_base,
@@ -328,7 +335,7 @@ __global__ __launch_bounds__(kEmitThreads, 4) void dec_emit_kernel(
     }
     const u32 n = list ? *list_count : n_chunks;
     for (u32 i = blockIdx.x; i < n; i += gridDim.x) {
-        dec_emit_chunk(tb, items, chunk_item, d_in, d_out, fn_tab, cp_tab, lane_count_tab, chunk_regular, chunk_entry, chunk_base, results, list ? list[i] : i);
+        dec_emit_chunk(tb, items, chunk_item, d_in, d_out, fn_tab, lane_rec, chunk_regular, chunk_entry, chunk_base, results, list ? list[i] : i);
         __syncthreads(); /* image and stage are reused by the next chunk */
     }
 }
@@ -374,8 +381,7 @@ __device__ __forceinline__ void dec_emit_fast_chunk(
     const hufd_chunk_rec *chunk_rec,
     const u8 *d_in,
     u8 *d_out,
-    const u16 *cp_tab,
-    const u16 *lane_count,
+    const hufd_lane_rec *lane_rec,
     const hufd_emit_rec *emit_rec,
     hufd_dec_result *results,
     u32 *slow_list, /* chunks left to dec_emit_kernel */
@@ -419,8 +425,6 @@ __device__ __forceinline__ void dec_emit_fast_chunk(
     }
     const u32 n_full = !TAIL ? HUFD_DEC_LANES : (valid >= 8u ? (u32)((valid - 8u) / HUFD_DEC_SUB_BYTES) : 0u);
     const u64 cbase = erec.base;
-    const u16 *cpt = cp_tab + (u64)c * kCpRows * HUFD_DEC_LANES;
-    const u32 merged_row = (kQuarters - 1) * HUFD_DEC_LANES;
     const u32 chunk_symbols = erec.symbols;
     /* all the same for the whole workgroup */
     const u32 regular = (erec.flags & HUFD_EMIT_REGULAR_MASK) >> HUFD_EMIT_REGULAR_SHIFT; /* 1: all lanes whole; 2: the chunk that holds the end of the stream */
@@ -449,6 +453,15 @@ __device__ __forceinline__ void dec_emit_fast_chunk(
     u32 w[kEmitChains][kRows + 1];
     u32 my_cp[kEmitChains], next_cp[kEmitChains], entry_state[kEmitChains], cnt[kEmitChains];
     bool whole[kEmitChains];
+    /* my two sub-chunks' records, 32 neighbouring bytes: the checkpoints on either side of my quarter and the lane's symbols
+     * come out of them in registers, and so does the state chain 1 is entered in -- how chain 0's sub-chunk leaves.  Chain
+     * 0's own entry is the one bit of its record's entry mask and not a load of the record in front: every kernel that
+     * writes a lane >= 1 of a regular chunk (dec_sync_one and its careful end, dec_sync_pack, dec_sync_guess,
+     * dec_sync_true, dec_sync_tail) writes 1 << entry there, the state the lane in front leaves in, and only regular
+     * chunks get here; lane 0's mask holds every state that reaches its walk, its entry is the chunk's ("One
+     * record a sub-chunk").  (A lane behind the whole ones has no bit: any state does, it is not walked.) */
+    const uint4 recs[kEmitChains] = {lane_rec_load(lane_rec, c, lanes[0]), lane_rec_load(lane_rec, c, lanes[1])};
+    const u32 entry_front = lanes[0] ? (u32)__builtin_ctz((lane_rec_merged(recs[0]) & 0xFFFu) | 0x1000u) : s0;
 #pragma unroll
     for (u32 ch = 0; ch < kEmitChains; ++ch) {
         sub[ch] = d_in + rec.src_off + (u64)lanes[ch] * HUFD_DEC_SUB_BYTES;
@@ -469,10 +482,13 @@ __device__ __forceinline__ void dec_emit_fast_chunk(
             }
             w[ch][kRows] = __builtin_bswap32(reinterpret_cast<const unaligned_u32 *>(sub[ch] + (q + 1) * kRows * 4)->x);
         }
-        my_cp[ch] = q ? cpt[(q - 1) * HUFD_DEC_LANES + lanes[ch]] : 0u;
-        next_cp[ch] = q + 1 < kQuarters ? cpt[q * HUFD_DEC_LANES + lanes[ch]] : 0u;
-        entry_state[ch] = lanes[ch] ? (u32)(cpt[merged_row + lanes[ch] - 1] >> 12) : s0;
-        cnt[ch] = lane_count[(u64)c * HUFD_DEC_LANES + lanes[ch]];
+        /* (checkpoint q - 1 is where my quarter starts, checkpoint q where the next one does: words x, y of the record as
+         * one 64-bit value, 16 bits a checkpoint, the merged word on top) */
+        const u64 cps = ((u64)recs[ch].y << 32) | recs[ch].x;
+        my_cp[ch] = q ? (u32)(cps >> (16u * (q - 1u))) & 0xFFFFu : 0u;
+        next_cp[ch] = q + 1 < kQuarters ? (u32)(cps >> (16u * q)) & 0xFFFFu : 0u;
+        entry_state[ch] = ch ? lane_rec_merged(recs[0]) >> 12 : entry_front;
+        cnt[ch] = lane_rec_count(recs[ch]);
     }
 #pragma unroll
     for (u32 j = 0; j < kLutPerThread; ++j) {
@@ -499,7 +515,7 @@ __device__ __forceinline__ void dec_emit_fast_chunk(
     u32 incl = 0, own_cnt = 0; /* thread t < 256 does this for sub-chunk t, whoever walks it */
     if (t < HUFD_DEC_LANES) {
         /* (TAIL: the lanes behind the stream's last two sub-chunks hold nothing; dec_sync_pack does not even write their records) */
-        own_cnt = t < n_full + 2 ? lane_count[(u64)c * HUFD_DEC_LANES + t] : 0u;
+        own_cnt = t < n_full + 2 ? lane_rec_count(lane_rec, c, t) : 0u;
         incl = wave_inclusive_sum(t ? own_cnt : 0u, t & (kWave - 1));
         if ((t & (kWave - 1)) == kWave - 1) {
             sh.wave_tot[t / kWave] = incl;
@@ -594,7 +610,9 @@ __device__ __forceinline__ void dec_emit_fast_chunk(
     if (extend) {
         /* rare: sub-chunk 0 on through the second quarter -- and the third and fourth when their checkpoints are missing too
          * (dec_sync_one: the walks of sub-chunk 0 met late) --, words straight from memory */
-        const u32 extend_end = (cpt[1 * HUFD_DEC_LANES] & 0x8000u) ? 2 * kRows : ((cpt[2 * HUFD_DEC_LANES] & 0x8000u) ? 3 * kRows : 4 * kRows);
+        /* (sub-chunk 0's record again, from memory: kept in registers through the walk for this it costs every thread two) */
+        const uint4 rec0 = lane_rec_load(lane_rec, c, 0);
+        const u32 extend_end = (lane_rec_cp(rec0, 1) & 0x8000u) ? 2 * kRows : ((lane_rec_cp(rec0, 2) & 0x8000u) ? 3 * kRows : 4 * kRows);
         u32 hi = w[0][kRows];
         for (u32 r = kRows; r < extend_end; ++r) {
             /* (sub-chunk 0: the address is rebuilt from the chunk's, so that no pointer has to stay in registers for this) */
@@ -645,8 +663,7 @@ __global__ __launch_bounds__(kEmitFastThreads, TAIL ? 6 : 8) void dec_emit_fast_
     const u32 *tail_chunks,
     const u8 *d_in,
     u8 *d_out,
-    const u16 *cp_tab,
-    const u16 *lane_count,
+    const hufd_lane_rec *lane_rec,
     const hufd_emit_rec *emit_rec,
     hufd_dec_result *results,
     u32 *slow_list, /* chunks left to dec_emit_kernel */
@@ -655,7 +672,7 @@ __global__ __launch_bounds__(kEmitFastThreads, TAIL ? 6 : 8) void dec_emit_fast_
     u32 *dense_count,
     u32 stage_limit /* symbols the stage of this launch holds (HUFD_DEC_STAGE_BYTES, or less: emit_lds_bytes) */) {
     dec_emit_fast_chunk<LB, TAIL, SURE>(
-        TAIL ? tail_chunks[blockIdx.x] : blockIdx.x, tb, chunk_rec, d_in, d_out, cp_tab, lane_count, emit_rec, results, slow_list,
+        TAIL ? tail_chunks[blockIdx.x] : blockIdx.x, tb, chunk_rec, d_in, d_out, lane_rec, emit_rec, results, slow_list,
         slow_count, dense_list, dense_count, stage_limit);
 }
 
@@ -673,8 +690,7 @@ __global__ __launch_bounds__(kEmitFastThreads, 4) void dec_emit_big_kernel(
     const hufd_chunk_rec *chunk_rec,
     const u8 *d_in,
     u8 *d_out,
-    const u16 *cp_tab,
-    const u16 *lane_count,
+    const hufd_lane_rec *lane_rec,
     const hufd_emit_rec *emit_rec,
     hufd_dec_result *results,
     u32 *slow_list,
@@ -688,7 +704,7 @@ __global__ __launch_bounds__(kEmitFastThreads, 4) void dec_emit_big_kernel(
         }
         /* (a chunk that does not go through here after all is left to the long way, not listed for this kernel again) */
         dec_emit_fast_chunk<LB, false, SURE>(
-            big_list[k], tb, chunk_rec, d_in, d_out, cp_tab, lane_count, emit_rec, results, slow_list, slow_count, slow_list,
+            big_list[k], tb, chunk_rec, d_in, d_out, lane_rec, emit_rec, results, slow_list, slow_count, slow_list,
             slow_count, kEmitBigStage);
         __syncthreads(); /* the table and the stage are written again */
     }
@@ -727,8 +743,7 @@ __global__ __launch_bounds__(kEmitFastThreads, 6) void dec_emit_pack_kernel(
     u32 slots,  /* slots a workgroup: what its threads and its LDS hold */
     const u8 *d_in,
     u8 *d_out,
-    const u16 *cp_tab,
-    const u16 *lane_count,
+    const hufd_lane_rec *lane_rec,
     const u8 *chunk_regular,
     const u32 *chunk_fn,
     const u32 *chunk_entry,
@@ -760,14 +775,12 @@ __global__ __launch_bounds__(kEmitFastThreads, 6) void dec_emit_pack_kernel(
     const u64 valid = rec.valid;
     const u32 n_full = valid >= 8u ? (u32)((valid - 8u) / HUFD_DEC_SUB_BYTES) : 0u;
     const u64 cbase = have ? chunk_base[c] : 0;
-    const u16 *cpt = cp_tab + (u64)c * kCpRows * HUFD_DEC_LANES;
-    const u32 merged_row = (kQuarters - 1) * HUFD_DEC_LANES;
     const u32 f0 = have ? chunk_fn[(u64)c * ns + s0] : 0u;
     const u32 chunk_symbols = wide_count(f0);
     const u32 regular = have ? chunk_regular[c] : 0u;
     /* (the stream ended before this chunk; fewer than 136 bytes: dec_emit_tail does the whole chunk) */
     const bool wanted = have && (centry & 0x100u) != 0 && regular != 3;
-    const bool fits = wanted && regular == 2 && ((cpt[merged_row] >> s0) & 1u) != 0 && cbase + chunk_symbols <= rec.out_cap;
+    const bool fits = wanted && regular == 2 && ((lane_rec_merged(lane_rec, c, 0) >> s0) & 1u) != 0 && cbase + chunk_symbols <= rec.out_cap;
     const bool fast = fits && chunk_symbols + 16 <= stage_limit && n_full + 2 <= slot_lanes &&
                       (lds_offset_of(sh.wlut) & ((4u << LB) - 1u)) == 0 && SURE <= row_walk(LB, tb.max_bits).sure;
     if (tt == 0 && slot < kPackMaxSlots) {
@@ -783,6 +796,7 @@ __global__ __launch_bounds__(kEmitFastThreads, 6) void dec_emit_pack_kernel(
     u32 w[kEmitChains][kRows + 1];
     u32 my_cp[kEmitChains], next_cp[kEmitChains], entry_state[kEmitChains], cnt[kEmitChains];
     bool whole[kEmitChains];
+    uint4 recs[kEmitChains] = {lane_rec_unreached(), lane_rec_unreached()};
 #pragma unroll
     for (u32 ch = 0; ch < kEmitChains; ++ch) {
         whole[ch] = fast && lanes[ch] < n_full;
@@ -803,10 +817,13 @@ __global__ __launch_bounds__(kEmitFastThreads, 6) void dec_emit_pack_kernel(
                 w[ch][4 * j + 3] = __builtin_bswap32(v.w);
             }
             w[ch][kRows] = __builtin_bswap32(reinterpret_cast<const unaligned_u32 *>(sub + (q + 1) * kRows * 4)->x);
-            my_cp[ch] = q ? cpt[(q - 1) * HUFD_DEC_LANES + lanes[ch]] : 0u;
-            next_cp[ch] = q + 1 < kQuarters ? cpt[q * HUFD_DEC_LANES + lanes[ch]] : 0u;
-            entry_state[ch] = lanes[ch] ? (u32)(cpt[merged_row + lanes[ch] - 1] >> 12) : s0;
-            cnt[ch] = lane_count[(u64)c * HUFD_DEC_LANES + lanes[ch]];
+            /* (the record as in dec_emit_fast; chain 1's entry is how chain 0's sub-chunk leaves, whole whenever chain 1's is) */
+            recs[ch] = lane_rec_load(lane_rec, c, lanes[ch]);
+            const u64 cps = ((u64)recs[ch].y << 32) | recs[ch].x;
+            my_cp[ch] = q ? (u32)(cps >> (16u * (q - 1u))) & 0xFFFFu : 0u;
+            next_cp[ch] = q + 1 < kQuarters ? (u32)(cps >> (16u * q)) & 0xFFFFu : 0u;
+            entry_state[ch] = ch ? lane_rec_merged(recs[0]) >> 12 : (lanes[0] ? lane_rec_merged(lane_rec, c, lanes[0] - 1) >> 12 : s0);
+            cnt[ch] = lane_rec_count(recs[ch]);
         }
     }
 #pragma unroll
@@ -827,7 +844,7 @@ __global__ __launch_bounds__(kEmitFastThreads, 6) void dec_emit_pack_kernel(
     if (t < HUFD_DEC_LANES) {
         const u32 sa = t / slot_lanes, la = t % slot_lanes;
         const u32 ca = sa < slots && sa < kPackMaxSlots ? sh.slot_chunk[sa] : HUFD_NONE32;
-        own = ca != HUFD_NONE32 && la != 0 && la < sh.slot_full[sa] + 2 && la < HUFD_DEC_LANES ? lane_count[(u64)ca * HUFD_DEC_LANES + la] : 0u;
+        own = ca != HUFD_NONE32 && la != 0 && la < sh.slot_full[sa] + 2 && la < HUFD_DEC_LANES ? lane_rec_count(lane_rec, ca, la) : 0u;
         incl = wave_inclusive_sum(own, t & (kWave - 1));
         if ((t & (kWave - 1)) == kWave - 1) {
             sh.wave_tot[t / kWave] = incl;
@@ -912,7 +929,8 @@ __global__ __launch_bounds__(kEmitFastThreads, 6) void dec_emit_pack_kernel(
     }
     if (extend) {
         /* rare: sub-chunk 0 on through the second quarter (and further while checkpoints are missing), words straight from memory */
-        const u32 extend_end = (cpt[1 * HUFD_DEC_LANES] & 0x8000u) ? 2 * kRows : ((cpt[2 * HUFD_DEC_LANES] & 0x8000u) ? 3 * kRows : 4 * kRows);
+        const uint4 rec0 = lane_rec_load(lane_rec, c, 0);
+        const u32 extend_end = (lane_rec_cp(rec0, 1) & 0x8000u) ? 2 * kRows : ((lane_rec_cp(rec0, 2) & 0x8000u) ? 3 * kRows : 4 * kRows);
         u32 hi = w[0][kRows];
         for (u32 r = kRows; r < extend_end; ++r) {
             const u32 lo = __builtin_bswap32(reinterpret_cast<const unaligned_u32 *>(d_in + rec.src_off + (r + 1) * 4)->x);
@@ -965,8 +983,7 @@ __global__ __launch_bounds__(kTailThreads) void dec_emit_tail_kernel(
     u32 n_tail,
     const u8 *d_in,
     u8 *d_out,
-    const u16 *cp_tab,
-    const u16 *lane_count,
+    const hufd_lane_rec *lane_rec,
     const u8 *chunk_regular,
     const u32 *chunk_fn,
     const u32 *chunk_entry,
@@ -1026,19 +1043,17 @@ __global__ __launch_bounds__(kTailThreads) void dec_emit_tail_kernel(
         }
         return;
     }
-    const u16 *cpt = cp_tab + (u64)c * kCpRows * HUFD_DEC_LANES;
-    const u32 merged_row = (kQuarters - 1) * HUFD_DEC_LANES;
     const u32 f0 = chunk_fn[(u64)c * ns + s0];
     const u32 chunk_symbols = wide_count(f0);
     /* exactly the chunks dec_emit_fast<TAIL> emitted in one pass (the two-pass and the long way do their own ends) */
-    if (((cpt[merged_row] >> s0) & 1u) == 0 || cbase + chunk_symbols > it.out_cap || chunk_symbols + 16 > stage_limit) {
+    if (((lane_rec_merged(lane_rec, c, 0) >> s0) & 1u) == 0 || cbase + chunk_symbols > it.out_cap || chunk_symbols + 16 > stage_limit) {
         return; /* (the same test, with the same stage, as dec_emit_fast<TAIL>'s `fast`: the two kernels run side by side) */
     }
     const u32 n_full = (u32)((valid - 8u) / HUFD_DEC_SUB_BYTES);
     const u32 first = n_full, second = n_full + 1;
-    const u32 n_first = lane_count[(u64)c * HUFD_DEC_LANES + first];
-    const u32 n_second = second < HUFD_DEC_LANES ? lane_count[(u64)c * HUFD_DEC_LANES + second] : 0u;
-    const u32 entry = cpt[merged_row + first - 1] >> 12;
+    const u32 n_first = lane_rec_count(lane_rec, c, first);
+    const u32 n_second = second < HUFD_DEC_LANES ? lane_rec_count(lane_rec, c, second) : 0u;
+    const u32 entry = lane_rec_merged(lane_rec, c, first - 1) >> 12;
     const u8 *tsrc = d_in + it.in_off + chunk_off + (u64)n_full * HUFD_DEC_SUB_BYTES;
     const u64 tail_bytes = valid - (u64)n_full * HUFD_DEC_SUB_BYTES;
     u32 *words = sh.words[threadIdx.x];
@@ -1091,7 +1106,7 @@ void hufk_host::decode_emit_stage(const struct hufk_decode_args *a, hipStream_t 
 hipLaunchKernelGGL(                                                                                                \
     (dec_emit_fast_kernel<LBV, TAILV, SUREV>), dim3(GRID), dim3((TAILV) && (LBV) == 10 ? tail_block : kEmitFastThreads), \
     emit_lds_bytes<LBV>(TAILV ? tail_stage : HUFD_DEC_STAGE_BYTES), STREAMV, a->tables, a->chunk_rec,              \
-    emit_single_chunks, (const u8 *)a->d_in, (u8 *)a->d_out, (const u16 *)a->cp_tab, (const u16 *)a->lane_count,   \
+    emit_single_chunks, (const u8 *)a->d_in, (u8 *)a->d_out, (const hufd_lane_rec *)a->lane_rec,                   \
     (const hufd_emit_rec *)a->emit_rec, a->results, a->emit_list, emit_count,                                      \
     !TAILV && big ? a->dense_list : a->emit_list, !TAILV && big ? dense_count : emit_count,                  \
     TAILV ? tail_stage : HUFD_DEC_STAGE_BYTES)
@@ -1138,8 +1153,8 @@ hipLaunchKernelGGL(                                                             
 hipLaunchKernelGGL(                                                                                                \
     (dec_emit_pack_kernel<LBV, SUREV>), dim3((e_packed + epack_slots - 1) / epack_slots), dim3(kEmitFastThreads),    \
     (uint32_t)sizeof(emit_pack_shared<LBV>) + epack_slots * epack_stage, tst, a->tables, a->chunk_rec, a->tail_chunks, \
-    e_packed, epack_width, epack_slots, (const u8 *)a->d_in, (u8 *)a->d_out, (const u16 *)a->cp_tab,               \
-    (const u16 *)a->lane_count, (const u8 *)a->chunk_regular, (const u32 *)a->chunk_fn, (const u32 *)a->chunk_entry, \
+    e_packed, epack_width, epack_slots, (const u8 *)a->d_in, (u8 *)a->d_out, (const hufd_lane_rec *)a->lane_rec,   \
+    (const u8 *)a->chunk_regular, (const u32 *)a->chunk_fn, (const u32 *)a->chunk_entry,                           \
     (const u64 *)a->chunk_base, a->emit_list, emit_count, tail_stage)
     /* chunks of short codes that hold more symbols than dec_emit_fast's stage: dec_emit_big where the chunk lies
      * inside its stream; the others take the long way (dec_emit) */
@@ -1181,7 +1196,7 @@ hipLaunchKernelGGL(                                                             
         hipLaunchKernelGGL(
             dec_emit_tail_kernel, dim3((a->n_tail + kTailThreads - 1) / kTailThreads), dim3(kTailThreads), lds, ends_st,
             a->tables, a->items, a->chunk_item, a->tail_chunks, a->n_tail, (const u8 *)a->d_in, (u8 *)a->d_out,
-            (const u16 *)a->cp_tab, (const u16 *)a->lane_count, (const u8 *)a->chunk_regular,
+            (const hufd_lane_rec *)a->lane_rec, (const u8 *)a->chunk_regular,
             (const u32 *)a->chunk_fn, (const u32 *)a->chunk_entry, (const u64 *)a->chunk_base, a->results, tail_stage);
     }
     if (have_side) {
@@ -1197,7 +1212,7 @@ do {                                                                            
         (dec_emit_big_kernel<LBV, SUREV>),                                                                         \
         dim3(persistent_grid(dec_emit_big_kernel<LBV, SUREV>, kEmitFastThreads, lds, a->n_chunks)),                 \
         dim3(kEmitFastThreads), lds, st, a->tables, a->chunk_rec, (const u8 *)a->d_in, (u8 *)a->d_out,             \
-        (const u16 *)a->cp_tab, (const u16 *)a->lane_count, (const hufd_emit_rec *)a->emit_rec, a->results,        \
+        (const hufd_lane_rec *)a->lane_rec, (const hufd_emit_rec *)a->emit_rec, a->results,                        \
         a->emit_list, emit_count,                                                                               \
         (const u32 *)a->dense_list, (const u32 *)dense_count);                                                  \
 } while (0)
@@ -1216,7 +1231,7 @@ do {                                                                            
         dec_emit_kernel,
         dim3(persistent_grid(dec_emit_kernel, kEmitThreads, dec_emit_lds_bytes(&a->tables), a->n_chunks)),
         dim3(kEmitThreads), dec_emit_lds_bytes(&a->tables), st, a->tables, a->items, a->chunk_item, a->n_chunks,
-        (const u8 *)a->d_in, (u8 *)a->d_out, a->fn_tab, a->cp_tab, (const u16 *)a->lane_count,
+        (const u8 *)a->d_in, (u8 *)a->d_out, a->fn_tab, (const hufd_lane_rec *)a->lane_rec,
         (const u8 *)a->chunk_regular, a->chunk_entry, a->chunk_base, a->results, (const u32 *)a->emit_list,
         (const u32 *)emit_count, a->counters, a->summary, a->counters_self_cleared);
 }

@@ -33,14 +33,14 @@ __device__ void dec_finish_item(
  * chunk's function of that state (not looked at for a chunk the stream does not reach).  The sync stage has run: what it
  * found of the chunk is in chunk_regular and in the last checkpoint row. */
 __device__ __forceinline__ hufd_emit_rec emit_rec_of(
-    u32 c, u32 state, bool stopped, u64 total, u32 f, const u8 *chunk_regular, const u16 *cp_tab) {
+    u32 c, u32 state, bool stopped, u64 total, u32 f, const u8 *chunk_regular, const hufd_lane_rec *lane_rec) {
     hufd_emit_rec r;
     r.flags = state & HUFD_EMIT_STATE_MASK;
     r.symbols = 0;
     r.base = total;
     if (!stopped) {
         const u32 regular = chunk_regular[c];
-        const u32 merged = cp_tab[((u64)c * kCpRows + (kQuarters - 1)) * HUFD_DEC_LANES];
+        const u32 merged = lane_rec_merged(lane_rec, c, 0);
         r.flags |= HUFD_EMIT_REACHED | (regular << HUFD_EMIT_REGULAR_SHIFT) | (((merged >> state) & 1u) ? HUFD_EMIT_MERGED : 0u) |
                    (wide_stop(f) ? HUFD_EMIT_STOPS : 0u);
         r.symbols = wide_count(f);
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void dec_scan_small_kernel(
     u32 ns,
     const u32 *chunk_fn,
     const u8 *chunk_regular,
-    const u16 *cp_tab,
+    const hufd_lane_rec *lane_rec,
     u32 *chunk_entry,
     u64 *chunk_base,
     hufd_emit_rec *emit_rec,
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(256) void dec_scan_small_kernel(
         chunk_entry[c] = entry_pack(state, !stopped);
         chunk_base[c] = total;
         const u32 f = stopped ? 0u : chunk_fn[(u64)c * ns + state];
-        emit_rec[c] = emit_rec_of(c, state, stopped, total, f, chunk_regular, cp_tab);
+        emit_rec[c] = emit_rec_of(c, state, stopped, total, f, chunk_regular, lane_rec);
         if (!stopped) {
             total += wide_count(f);
             stopped = wide_stop(f);
@@ -209,7 +209,7 @@ __global__ __launch_bounds__(256) void dec_scan_apply_kernel(
     const u32 *chunk_fn,
     const u32 *run_fn,
     const u8 *chunk_regular,
-    const u16 *cp_tab,
+    const hufd_lane_rec *lane_rec,
     u32 *chunk_entry,
     u64 *chunk_base,
     hufd_emit_rec *emit_rec,
@@ -273,7 +273,7 @@ __global__ __launch_bounds__(256) void dec_scan_apply_kernel(
         const u32 centry = chunk_entry[c];
         const u32 state = centry & 0xFFu;
         const bool stopped = !(centry & 0x100u);
-        emit_rec[c] = emit_rec_of(c, state, stopped, chunk_base[c], stopped ? 0u : fn[q * ns + state], chunk_regular, cp_tab);
+        emit_rec[c] = emit_rec_of(c, state, stopped, chunk_base[c], stopped ? 0u : fn[q * ns + state], chunk_regular, lane_rec);
     }
 }
 
@@ -558,7 +558,7 @@ static int decode_launch_stages(const struct hufk_decode_args *a, const struct h
     if (a->n_tiny != a->n_items && a->n_large != a->n_items) { /* (as in the encoder: nothing to scan, and no empty item's record to write, in a plan of thread-per-item items only; nor in one of long items only -- one stream --, which are dec_scan_runs / _top / _apply's) */
         hipLaunchKernelGGL(
             dec_scan_small_kernel, dim3((a->n_items + 255) / 256), dim3(256), 0, st, a->items, a->n_items, ns, a->chunk_fn,
-            (const u8 *)a->chunk_regular, (const u16 *)a->cp_tab, a->chunk_entry, a->chunk_base, a->emit_rec, a->states, a->results);
+            (const u8 *)a->chunk_regular, (const hufd_lane_rec *)a->lane_rec, a->chunk_entry, a->chunk_base, a->emit_rec, a->states, a->results);
     }
     hufk_host::decode_items_stage(items_pass, st);
     if (a->n_large) {
@@ -567,7 +567,7 @@ static int decode_launch_stages(const struct hufk_decode_args *a, const struct h
             dec_scan_runs_kernel, dim3(a->n_runs), dim3(256), lds, st, a->items, a->runs, ns, a->chunk_fn, a->run_fn);
         hipLaunchKernelGGL(
             dec_scan_apply_kernel, dim3(a->n_runs), dim3(256), scan_apply_lds_bytes(ns), st, a->items, a->runs, ns, a->chunk_fn,
-            (const u32 *)a->run_fn, (const u8 *)a->chunk_regular, (const u16 *)a->cp_tab, a->chunk_entry, a->chunk_base,
+            (const u32 *)a->run_fn, (const u8 *)a->chunk_regular, (const hufd_lane_rec *)a->lane_rec, a->chunk_entry, a->chunk_base,
             a->emit_rec, a->states, a->results);
     }
     hufk_host::decode_sync_true_stage(a, st, state);

@@ -41,7 +41,7 @@ __device__ __forceinline__ void dec_sync_chunk(
     const u32 *chunk_item,
     const u8 *d_in,
     u16 *fn_tab,   /* [chunk][state][lane] */
-    u16 *cp_tab,   /* [chunk][kCpRows][lane]: checkpoints of the reference walk + merged-state mask */
+    hufd_lane_rec *lane_rec, /* [chunk][lane]: checkpoints of the reference walk + merged-state mask (no count: the long way has the lane functions) */
     u32 *chunk_fn, /* [chunk][state] */
     u8 *chunk_regular,      /* [chunk]: cleared here */
     u32 c) {
@@ -180,12 +180,11 @@ __device__ __forceinline__ void dec_sync_chunk(
     }
     {
         /* checkpoint: [15] usable, [14:11] bits past the quarter boundary, [10:0] symbols from it to the end of the walk */
-        u16 *cp = cp_tab + (u64)c * kCpRows * HUFD_DEC_LANES + lane;
+        u32 cps[kQuarters - 1];
 #pragma unroll
         for (u32 qq = 0; qq + 1 < kQuarters; ++qq) {
             const u32 tail = ref_steps - cp_steps[qq];
-            cp[qq * HUFD_DEC_LANES] =
-                (u16)(cp_ok[qq] ? 0x8000u | ((cp_pos[qq] - (qq + 1) * kQuarterBits) << 11) | tail : 0u);
+            cps[qq] = cp_ok[qq] ? 0x8000u | ((cp_pos[qq] - (qq + 1) * kQuarterBits) << 11) | tail : 0u;
         }
         u32 merged = 0; /* entry states whose walk runs into the reference walk */
 #pragma unroll
@@ -194,7 +193,8 @@ __device__ __forceinline__ void dec_sync_chunk(
         }
         /* [15:12] where every merged state comes out: exit state, kExitStop, or kExitNoRef without a reference walk */
         const u32 common = have_ref ? (ref_stop ? kExitStop : ref_exit) : kExitNoRef;
-        cp[(kQuarters - 1) * HUFD_DEC_LANES] = (u16)(merged | (common << 12));
+        /* (no count: the chunk is not regular, dec_emit takes its lanes' symbols from the lane functions) */
+        lane_rec_store(lane_rec, c, lane, lane_rec_pack(cps[0], cps[1], cps[2], merged | (common << 12), 0));
     }
     __syncthreads();
 
@@ -222,7 +222,7 @@ __global__ __launch_bounds__(HUFD_DEC_LANES) void dec_sync_kernel(
     u32 n_chunks,
     const u8 *d_in,
     u16 *fn_tab,
-    u16 *cp_tab,
+    hufd_lane_rec *lane_rec,
     u32 *chunk_fn,
     u8 *chunk_regular,
     const u32 *list,
@@ -240,7 +240,7 @@ __global__ __launch_bounds__(HUFD_DEC_LANES) void dec_sync_kernel(
         if (list && chunk_regular[c] == kRegularFew) {
             continue; /* dec_sync_few, in front of this kernel on the same list, took it */
         }
-        dec_sync_chunk<NS>(tb, items, chunk_item, d_in, fn_tab, cp_tab, chunk_fn, chunk_regular, c);
+        dec_sync_chunk<NS>(tb, items, chunk_item, d_in, fn_tab, lane_rec, chunk_fn, chunk_regular, c);
         __syncthreads(); /* the image is loaded anew for the next chunk */
     }
 }
@@ -379,9 +379,8 @@ __global__ __launch_bounds__(HUFD_DEC_LANES, 8) void dec_sync_one_kernel(
     const u32 *tail_chunks,
     const u8 *d_in,
     u16 *fn_tab,
-    u16 *cp_tab,
+    hufd_lane_rec *lane_rec,
     u32 *chunk_fn,
-    u16 *lane_count,
     u8 *chunk_regular,
     u32 *tail_entry, /* [chunk] TAIL: the state in which the last whole lane leaves (dec_sync_tail picks it up) */
     u32 *slow_list,  /* chunks inside a stream that are not regular by this kernel's rules but whose first sub-chunk's
@@ -409,9 +408,8 @@ __global__ __launch_bounds__(HUFD_DEC_LANES, 8) void dec_sync_one_mixed_kernel(
     u32 n_tail,
     const u8 *d_in,
     u16 *fn_tab,
-    u16 *cp_tab,
+    hufd_lane_rec *lane_rec,
     u32 *chunk_fn,
-    u16 *lane_count,
     u8 *chunk_regular,
     u32 *tail_entry,
     u32 *slow_list,
@@ -467,9 +465,8 @@ __global__ __launch_bounds__(HUFD_DEC_LANES, 6) void dec_sync_pack_kernel(
     u32 width, /* lanes a slot: >= 16, >= the whole lanes of every chunk of the launch, <= 128 */
     const u8 *d_in,
     u16 *fn_tab,
-    u16 *cp_tab,
+    hufd_lane_rec *lane_rec,
     u32 *chunk_fn,
-    u16 *lane_count,
     u8 *chunk_regular,
     u32 *tail_entry,
     u32 *long_list,
@@ -523,7 +520,6 @@ __global__ __launch_bounds__(HUFD_DEC_LANES, 6) void dec_sync_pack_kernel(
         mine = false;
     }
     const bool active = mine && lane < n_full;
-    u16 *cp = cp_tab + (u64)c * kCpRows * HUFD_DEC_LANES;
     u32 w[kFastRows];
     {
         const u32 from = active ? lane : 0u;
@@ -663,7 +659,7 @@ __global__ __launch_bounds__(HUFD_DEC_LANES, 6) void dec_sync_pack_kernel(
 
     /* the tables dec_scan and dec_emit read (the regular chunks' format) */
     if (active) {
-        u16 *mcp = cp + lane;
+        u32 cps[kQuarters - 1];
 #pragma unroll
         for (u32 qq = 0; qq + 1 < kQuarters; ++qq) {
             const bool usable = (qq + 1) * (kSubWords / kQuarters) >= meet_row;
@@ -674,23 +670,16 @@ __global__ __launch_bounds__(HUFD_DEC_LANES, 6) void dec_sync_pack_kernel(
                 bits = rw.offset_of(head_cp);
                 have_cp = true;
             }
-            mcp[qq * HUFD_DEC_LANES] = (u16)(have_cp ? 0x8000u | (bits << 11) | tail : 0u);
+            cps[qq] = have_cp ? 0x8000u | (bits << 11) | tail : 0u;
         }
-        lane_count[(u64)c * HUFD_DEC_LANES + lane] = (u16)(lane ? count : ref_count);
-        mcp[(kQuarters - 1) * HUFD_DEC_LANES] = (u16)((lane ? 1u << entry : sh.alive[slot]) | (ref_exit << 12));
+        lane_rec_store(lane_rec, c, lane, lane_rec_pack(cps[0], cps[1], cps[2], (lane ? 1u << entry : sh.alive[slot]) | (ref_exit << 12), lane ? count : ref_count));
     }
     /* the chunk's lanes behind the whole ones: never reached, as far as this kernel knows (dec_sync_tail follows the true
      * path through the one or two sub-chunks the stream ends in and rewrites their records) */
     if (lane < 2 && n_full + lane < HUFD_DEC_LANES) {
         /* (the two sub-chunks the stream can end in; dec_emit_fast<TAIL> takes the lanes behind them as empty without
          * looking: writing a record for each of the chunk's 256 lanes cost this kernel more than its walks) */
-        const u32 l = n_full + lane;
-#pragma unroll
-        for (u32 qq = 0; qq + 1 < kQuarters; ++qq) {
-            cp[qq * HUFD_DEC_LANES + l] = 0;
-        }
-        lane_count[(u64)c * HUFD_DEC_LANES + l] = 0;
-        cp[(kQuarters - 1) * HUFD_DEC_LANES + l] = (u16)(kExitStop << 12);
+        lane_rec_store(lane_rec, c, n_full + lane, lane_rec_unreached());
     }
     if (lane + 1 == n_full) {
         tail_entry[c] = ref_exit;
@@ -739,9 +728,8 @@ __device__ __forceinline__ void dec_sync_guess_chunk(
     const hufd_chunk_rec *chunk_rec,
     const u8 *d_in,
     u16 *fn_tab,
-    u16 *cp_tab,
+    hufd_lane_rec *lane_rec,
     u32 *chunk_fn,
-    u16 *lane_count,
     u8 *chunk_regular,
     u32 *slow_list,
     u32 *slow_count) {
@@ -964,16 +952,15 @@ __device__ __forceinline__ void dec_sync_guess_chunk(
     u32 lane_o = lane;
     opaque(lane_o);
     u16 *fn_out = fn_tab + (u64)c * ns * HUFD_DEC_LANES;
-    u16 *cp = cp_tab + (u64)c * kCpRows * HUFD_DEC_LANES + lane_o;
+    u32 cps[kQuarters - 1];
 #pragma unroll
     for (u32 qq = 0; qq + 1 < kQuarters; ++qq) {
         /* lane 0: a checkpoint in front of the meeting row is not on its walk (dec_emit_fast goes on from the chunk's entry) */
         const bool have = lane != 0 || (qq + 1) * (kSubWords / kQuarters) >= meet_row;
         const u32 tail = count - (cp_state[qq] >> 16), bits = rw.offset_of(cp_state[qq]);
-        cp[qq * HUFD_DEC_LANES] = (u16)(have ? 0x8000u | (bits << 11) | tail : 0u);
+        cps[qq] = have ? 0x8000u | (bits << 11) | tail : 0u;
     }
-    lane_count[(u64)c * HUFD_DEC_LANES + lane_o] = (u16)count;
-    cp[(kQuarters - 1) * HUFD_DEC_LANES] = (u16)((lane ? 1u << entry : (u32)cand_alive) | (exit_bit << 12));
+    lane_rec_store(lane_rec, c, lane_o, lane_rec_pack(cps[0], cps[1], cps[2], (lane ? 1u << entry : (u32)cand_alive) | (exit_bit << 12), count));
     if (lane == 0) {
         chunk_regular[c] = 1;
     }
@@ -998,9 +985,8 @@ __global__ __launch_bounds__(HUFD_DEC_LANES, 4) void dec_sync_guess_kernel(
     const hufd_chunk_rec *chunk_rec,
     const u8 *d_in,
     u16 *fn_tab,
-    u16 *cp_tab,
+    hufd_lane_rec *lane_rec,
     u32 *chunk_fn,
-    u16 *lane_count,
     u8 *chunk_regular,
     const u32 *given_up,       /* dec_sync_one's list ... */
     const u32 *given_up_count,
@@ -1016,7 +1002,7 @@ __global__ __launch_bounds__(HUFD_DEC_LANES, 4) void dec_sync_guess_kernel(
             }
             continue;
         }
-        dec_sync_guess_chunk<LB, SURE>(c, tb, chunk_rec, d_in, fn_tab, cp_tab, chunk_fn, lane_count, chunk_regular, slow_list, slow_count);
+        dec_sync_guess_chunk<LB, SURE>(c, tb, chunk_rec, d_in, fn_tab, lane_rec, chunk_fn, chunk_regular, slow_list, slow_count);
         __syncthreads(); /* the tables in LDS are written again */
     }
 }
@@ -1093,7 +1079,7 @@ __global__ __launch_bounds__(HUFD_DEC_LANES, 4) void dec_sync_few_kernel(
     const hufd_chunk_rec *chunk_rec,
     const u8 *d_in,
     u16 *fn_tab,
-    u16 *cp_tab,
+    hufd_lane_rec *lane_rec,
     u32 *chunk_fn,
     u8 *chunk_regular,
     const u32 *list, /* what the kernels in front gave up; dec_sync, behind this one, goes through it again and skips the chunks marked here */
@@ -1184,12 +1170,8 @@ __global__ __launch_bounds__(HUFD_DEC_LANES, 4) void dec_sync_few_kernel(
             fn_tab[((u64)c * ns + s) * HUFD_DEC_LANES + lane] = sh.ftab[s * HUFD_DEC_LANES + lane];
         }
         {
-            u16 *cp = cp_tab + (u64)c * kCpRows * HUFD_DEC_LANES + lane;
-#pragma unroll
-            for (u32 qq = 0; qq + 1 < kQuarters; ++qq) {
-                cp[qq * HUFD_DEC_LANES] = 0;
-            }
-            cp[(kQuarters - 1) * HUFD_DEC_LANES] = (u16)(kExitNoRef << 12);
+            /* (no count either: dec_sync_true, behind the scan, writes the record anew or leaves the chunk to the long way) */
+            lane_rec_store(lane_rec, c, lane, lane_rec_pack(0, 0, 0, kExitNoRef << 12, 0));
         }
         __syncthreads();
         if (lane < kGroups * ns) {
@@ -1217,8 +1199,7 @@ __global__ __launch_bounds__(HUFD_DEC_LANES, 8) void dec_sync_true_kernel(
     const hufd_chunk_rec *chunk_rec,
     const u8 *d_in,
     const u16 *fn_tab,
-    u16 *cp_tab,
-    u16 *lane_count,
+    hufd_lane_rec *lane_rec,
     u8 *chunk_regular,
     const u32 *chunk_entry,
     hufd_emit_rec *emit_rec, /* the scan stage's, made while the chunk was still marked kRegularFew: what is decided here goes in */
@@ -1293,14 +1274,14 @@ __global__ __launch_bounds__(HUFD_DEC_LANES, 8) void dec_sync_true_kernel(
         const bool good = sh.bad == 0;
         __syncthreads();
         if (good) {
-            u16 *cp = cp_tab + (u64)c * kCpRows * HUFD_DEC_LANES + lane;
+            /* (all five values of the record are this kernel's: dec_sync_few left no checkpoint, no count, no exit) */
+            u32 cps[kQuarters - 1];
 #pragma unroll
             for (u32 qq = 0; qq + 1 < kQuarters; ++qq) {
                 const u32 tail = count - (cp_state[qq] >> 16), bits = rw.offset_of(cp_state[qq]);
-                cp[qq * HUFD_DEC_LANES] = (u16)(bits < 16u ? 0x8000u | (bits << 11) | tail : 0u);
+                cps[qq] = bits < 16u ? 0x8000u | (bits << 11) | tail : 0u;
             }
-            lane_count[(u64)c * HUFD_DEC_LANES + lane] = (u16)count;
-            cp[(kQuarters - 1) * HUFD_DEC_LANES] = (u16)((1u << entry) | (ex << 12));
+            lane_rec_store(lane_rec, c, lane, lane_rec_pack(cps[0], cps[1], cps[2], (1u << entry) | (ex << 12), count));
         }
         if (lane == 0) {
             chunk_regular[c] = good ? 1 : 0;
@@ -1323,9 +1304,8 @@ __global__ __launch_bounds__(kTailThreads) void dec_sync_tail_kernel(
     const u8 *chunk_regular,
     const u32 *tail_entry,
     u16 *fn_tab,
-    u16 *cp_tab,
-    u32 *chunk_fn,
-    u16 *lane_count) {
+    hufd_lane_rec *lane_rec,
+    u32 *chunk_fn) {
 
     tail_lds &sh = *reinterpret_cast<tail_lds *>(dyn_lds);
     u16 *lut = reinterpret_cast<u16 *>(dyn_lds + sizeof(tail_lds));
@@ -1371,7 +1351,6 @@ __global__ __launch_bounds__(kTailThreads) void dec_sync_tail_kernel(
 
     /* the records of the one or two lanes the true path gets to */
     u16 *fn_out = fn_tab + (u64)c * ns * HUFD_DEC_LANES;
-    u16 *cp = cp_tab + (u64)c * kCpRows * HUFD_DEC_LANES;
     for (u32 k = 0; k < 2; ++k) {
         const u32 lane = n_full + k;
         const bool reached = k == 0 || tw.stop != 0;
@@ -1380,10 +1359,10 @@ __global__ __launch_bounds__(kTailThreads) void dec_sync_tail_kernel(
         }
         const u32 my_entry = k == 0 ? entry : tw.exit;
         const bool stops_here = tw.stop == k;
-        lane_count[(u64)c * HUFD_DEC_LANES + lane] = (u16)tw.count[k];
         fn_out[(u64)my_entry * HUFD_DEC_LANES + lane] =
             stops_here ? fn_pack(true, 0, tw.count[k] & 0x7FFu) : fn_pack(false, tw.exit, tw.count[k] & 0x7FFu);
-        cp[(kQuarters - 1) * HUFD_DEC_LANES + lane] = (u16)((1u << my_entry) | ((stops_here ? kExitStop : tw.exit) << 12));
+        /* (no checkpoints, as the kernel in front of this one left the record: the lane is walked symbol by symbol) */
+        lane_rec_store(lane_rec, c, lane, lane_rec_pack(0, 0, 0, (1u << my_entry) | ((stops_here ? kExitStop : tw.exit) << 12), tw.count[k]));
     }
     /* the chunk function: every walk that gets through sub-chunk 0 goes on to the end of the stream */
     const bool stops = tw.stop != 2u;
@@ -1461,27 +1440,27 @@ if (folded) {                                                                   
     hipLaunchKernelGGL(                                                                                            \
         (dec_sync_one_mixed_kernel<LBV, SUREV>), dim3(a->n_chunks + a->n_tail), dim3(HUFD_DEC_LANES),              \
         (uint32_t)sizeof(one_shared<LBV>), st, a->tables, a->chunk_rec, a->tail_chunks, a->n_tail,                  \
-        (const u8 *)a->d_in, a->fn_tab, a->cp_tab, a->chunk_fn, a->lane_count, a->chunk_regular, a->tail_entry,     \
+        (const u8 *)a->d_in, a->fn_tab, a->lane_rec, a->chunk_fn, a->chunk_regular, a->tail_entry,                 \
         a->slow_list, slow_count, lean_long_list, lean_long_count);                                                \
 } else if (n_packed) {                                                                                                    \
     hipLaunchKernelGGL(                                                                                            \
         (dec_sync_pack_kernel<LBV, SUREV>), dim3((n_packed + pack_slots - 1) / pack_slots), dim3(HUFD_DEC_LANES),   \
         (uint32_t)sizeof(pack_shared<LBV>), tst, a->tables, a->chunk_rec, a->tail_chunks, n_packed, pack_width,     \
-        (const u8 *)a->d_in, a->fn_tab, a->cp_tab, a->chunk_fn, a->lane_count, a->chunk_regular, a->tail_entry,     \
+        (const u8 *)a->d_in, a->fn_tab, a->lane_rec, a->chunk_fn, a->chunk_regular, a->tail_entry,                 \
         lean_long_list, lean_long_count);                                                                          \
 }                                                                                                                  \
 if (!folded && n_single) {                                                                                         \
     hipLaunchKernelGGL(                                                                                            \
         (dec_sync_one_kernel<LBV, SUREV, true>), dim3(n_single), dim3(HUFD_DEC_LANES),                              \
         (uint32_t)sizeof(one_shared<LBV>), tst, a->tables, a->chunk_rec, single_chunks,                             \
-        (const u8 *)a->d_in, a->fn_tab, a->cp_tab, a->chunk_fn, a->lane_count, a->chunk_regular, a->tail_entry,     \
+        (const u8 *)a->d_in, a->fn_tab, a->lane_rec, a->chunk_fn, a->chunk_regular, a->tail_entry,                 \
         a->slow_list, slow_count, lean_long_list, lean_long_count);                                                \
 }                                                                                                                  \
 if (!folded && some_inside) {                                                                                      \
     hipLaunchKernelGGL(                                                                                            \
         (dec_sync_one_kernel<LBV, SUREV, false>), dim3(a->n_chunks), dim3(HUFD_DEC_LANES),                          \
         (uint32_t)sizeof(one_shared<LBV>), st, a->tables, a->chunk_rec, a->tail_chunks,                             \
-        (const u8 *)a->d_in, a->fn_tab, a->cp_tab, a->chunk_fn, a->lane_count, a->chunk_regular, a->tail_entry,     \
+        (const u8 *)a->d_in, a->fn_tab, a->lane_rec, a->chunk_fn, a->chunk_regular, a->tail_entry,                 \
         a->slow_list, slow_count, lean_long_list, lean_long_count);                                                \
 }
     if (lb_of_launch == 10) {
@@ -1499,7 +1478,7 @@ if (!folded && some_inside) {                                                   
         hipLaunchKernelGGL(
             dec_sync_tail_kernel, dim3((a->n_tail + kTailThreads - 1) / kTailThreads), dim3(kTailThreads), lds, tst,
             a->tables, a->items, a->chunk_item, a->tail_chunks, a->n_tail, (const u8 *)a->d_in,
-            (const u8 *)a->chunk_regular, (const u32 *)a->tail_entry, a->fn_tab, a->cp_tab, a->chunk_fn, a->lane_count);
+            (const u8 *)a->chunk_regular, (const u32 *)a->tail_entry, a->fn_tab, a->lane_rec, a->chunk_fn);
     }
     if (beside) {
         (void)hipEventRecord((hipEvent_t)a->join_event, tst);
@@ -1515,7 +1494,7 @@ hipLaunchKernelGGL(                                                             
     dim3(persistent_grid(dec_sync_guess_kernel<LBV, SUREV>, HUFD_DEC_LANES, (uint32_t)sizeof(lean_shared<LBV>),     \
                          a->n_chunks)),                                                                            \
     dim3(HUFD_DEC_LANES), (uint32_t)sizeof(lean_shared<LBV>), st, a->tables, a->chunk_rec, (const u8 *)a->d_in,     \
-    a->fn_tab, a->cp_tab, a->chunk_fn, a->lane_count, a->chunk_regular, (const u32 *)a->slow_list,                 \
+    a->fn_tab, a->lane_rec, a->chunk_fn, a->chunk_regular, (const u32 *)a->slow_list,                              \
     (const u32 *)slow_count, a->emit_list, a->counters + HUFK_DEC_COUNT_LONG)
         if (lb_of_launch == 10) {
             switch (sure) {
@@ -1537,20 +1516,20 @@ hipLaunchKernelGGL(                                                             
                     (dec_sync_few_kernel<10>),
                     dim3(persistent_grid(dec_sync_few_kernel<10>, HUFD_DEC_LANES, (uint32_t)sizeof(few_shared<10>), a->n_chunks)),
                     dim3(HUFD_DEC_LANES), (uint32_t)sizeof(few_shared<10>), st, a->tables, a->chunk_rec, (const u8 *)a->d_in,
-                    a->fn_tab, a->cp_tab, a->chunk_fn, a->chunk_regular, long_list, long_count, a->slow_list, few_count);
+                    a->fn_tab, a->lane_rec, a->chunk_fn, a->chunk_regular, long_list, long_count, a->slow_list, few_count);
             } else {
                 hipLaunchKernelGGL(
                     (dec_sync_few_kernel<12>),
                     dim3(persistent_grid(dec_sync_few_kernel<12>, HUFD_DEC_LANES, (uint32_t)sizeof(few_shared<12>), a->n_chunks)),
                     dim3(HUFD_DEC_LANES), (uint32_t)sizeof(few_shared<12>), st, a->tables, a->chunk_rec, (const u8 *)a->d_in,
-                    a->fn_tab, a->cp_tab, a->chunk_fn, a->chunk_regular, long_list, long_count, a->slow_list, few_count);
+                    a->fn_tab, a->lane_rec, a->chunk_fn, a->chunk_regular, long_list, long_count, a->slow_list, few_count);
             }
         }
     }
     hipLaunchKernelGGL(
         sync, dim3(persistent_grid(sync, HUFD_DEC_LANES, dec_sync_lds_bytes(&a->tables), a->n_chunks)),
         dim3(HUFD_DEC_LANES), dec_sync_lds_bytes(&a->tables), st, a->tables, a->items, a->chunk_item, a->n_chunks,
-        (const u8 *)a->d_in, a->fn_tab, a->cp_tab, a->chunk_fn, a->chunk_regular, long_list, long_count,
+        (const u8 *)a->d_in, a->fn_tab, a->lane_rec, a->chunk_fn, a->chunk_regular, long_list, long_count,
         a->counters_self_cleared ? a->counters : (u32 *)nullptr);
     s.few = few;
 }
@@ -1565,14 +1544,14 @@ void hufk_host::decode_sync_true_stage(const struct hufk_decode_args *a, hipStre
             (dec_sync_true_kernel<10>),
             dim3(persistent_grid(dec_sync_true_kernel<10>, HUFD_DEC_LANES, (uint32_t)sizeof(few_shared<10>), a->n_chunks)),
             dim3(HUFD_DEC_LANES), (uint32_t)sizeof(few_shared<10>), st, a->tables, a->chunk_rec, (const u8 *)a->d_in,
-            (const u16 *)a->fn_tab, a->cp_tab, a->lane_count, a->chunk_regular, (const u32 *)a->chunk_entry,
+            (const u16 *)a->fn_tab, a->lane_rec, a->chunk_regular, (const u32 *)a->chunk_entry,
             a->emit_rec, (const u32 *)a->slow_list, (const u32 *)(a->counters + HUFK_DEC_COUNT_FEW));
     } else {
         hipLaunchKernelGGL(
             (dec_sync_true_kernel<12>),
             dim3(persistent_grid(dec_sync_true_kernel<12>, HUFD_DEC_LANES, (uint32_t)sizeof(few_shared<12>), a->n_chunks)),
             dim3(HUFD_DEC_LANES), (uint32_t)sizeof(few_shared<12>), st, a->tables, a->chunk_rec, (const u8 *)a->d_in,
-            (const u16 *)a->fn_tab, a->cp_tab, a->lane_count, a->chunk_regular, (const u32 *)a->chunk_entry,
+            (const u16 *)a->fn_tab, a->lane_rec, a->chunk_regular, (const u32 *)a->chunk_entry,
             a->emit_rec, (const u32 *)a->slow_list, (const u32 *)(a->counters + HUFK_DEC_COUNT_FEW));
     }
 }

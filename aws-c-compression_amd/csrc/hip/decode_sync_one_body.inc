@@ -62,7 +62,6 @@
         }
         return;
     }
-    u16 *cp = cp_tab + (u64)c * kCpRows * HUFD_DEC_LANES + lane;
     constexpr u32 kLutPerLane = (1u << LB) / HUFD_DEC_LANES, kLutBatch = 4;
     const auto table_share = [&](u32 j0) {
         u32 lut_raw[kLutBatch];
@@ -83,12 +82,7 @@
         }
         /* (FOLLOW: the records of the one or two lanes the stream ends in are the following thread's to write) */
         if (!FOLLOW || (lane != n_full && lane != n_full + 1)) {
-#pragma unroll
-            for (u32 qq = 0; qq + 1 < kQuarters; ++qq) {
-                cp[qq * HUFD_DEC_LANES] = 0;
-            }
-            lane_count[(u64)c * HUFD_DEC_LANES + lane] = 0;
-            cp[(kQuarters - 1) * HUFD_DEC_LANES] = (u16)(kExitStop << 12);
+            lane_rec_store(lane_rec, c, lane, lane_rec_unreached());
         }
         return;
     }
@@ -293,8 +287,10 @@
     }
     __syncthreads();
     const bool stay = sh.moved != 0; /* (the same for the workgroup) */
-    auto lane_records = [&]() {
+    /* my sub-chunk's record, one store: the checkpoints, how the lane is entered and left, its symbols */
+    auto lane_record = [&](u32 merged, u32 symbols) {
         if (active) {
+            u32 cps[kQuarters - 1];
 #pragma unroll
             for (u32 qq = 0; qq + 1 < kQuarters; ++qq) {
                 /* a checkpoint in front of the meeting row is not on the guessed walk's true part: it is taken from the walk
@@ -309,16 +305,12 @@
                     bits = ow.offset_of(head_cp[qq]);
                     have = true;
                 }
-                cp[qq * HUFD_DEC_LANES] = (u16)(have ? 0x8000u | (bits << 11) | tail : 0u);
+                cps[qq] = have ? 0x8000u | (bits << 11) | tail : 0u;
             }
+            lane_rec_store(lane_rec, c, lane, lane_rec_pack(cps[0], cps[1], cps[2], merged, symbols));
         } else if (!FOLLOW || (lane != n_full && lane != n_full + 1)) {
             /* (TAIL) behind the whole lanes, in a wave that has some: as for the waves that left */
-#pragma unroll
-            for (u32 qq = 0; qq + 1 < kQuarters; ++qq) {
-                cp[qq * HUFD_DEC_LANES] = 0;
-            }
-            lane_count[(u64)c * HUFD_DEC_LANES + lane] = 0;
-            cp[(kQuarters - 1) * HUFD_DEC_LANES] = (u16)(kExitStop << 12);
+            lane_rec_store(lane_rec, c, lane, lane_rec_unreached());
         }
         if (TAIL && lane + 1 == n_full) {
             tail_entry[c] = ref_exit;
@@ -326,11 +318,7 @@
     };
     if (!stay && lane >= kWave) {
         if (!sh.bad && !sh.bad_mine) {
-            lane_records();
-            if (active) {
-                lane_count[(u64)c * HUFD_DEC_LANES + lane] = (u16)count;
-                cp[(kQuarters - 1) * HUFD_DEC_LANES] = (u16)((1u << entry) | (ref_exit << 12));
-            }
+            lane_record((1u << entry) | (ref_exit << 12), count);
         }
         return;
     }
@@ -514,12 +502,8 @@
 
     /* the tables dec_scan and dec_emit read (the regular chunks' format) */
     u16 *fn_out = fn_tab + (u64)c * ns * HUFD_DEC_LANES;
-    lane_records();
-    if (active) {
-        const u32 total = lane ? count : ref_count0; /* (lane 0: from where its walk is the true one) */
-        lane_count[(u64)c * HUFD_DEC_LANES + lane] = (u16)total;
-        cp[(kQuarters - 1) * HUFD_DEC_LANES] = (u16)((lane ? 1u << entry : (u32)cand_alive) | (ref_exit << 12));
-    }
+    /* (lane 0: its symbols from where its walk is the true one, and the entry states that get there) */
+    lane_record((lane ? 1u << entry : (u32)cand_alive) | (ref_exit << 12), lane ? count : ref_count0);
     if (lane == 0) {
         chunk_regular[c] = TAIL ? 2 : 1;
     }
@@ -555,22 +539,15 @@
                 if (ln >= HUFD_DEC_LANES) {
                     break;
                 }
-                u16 *cpl = cp_tab + (u64)c * kCpRows * HUFD_DEC_LANES + ln;
                 const bool reached = k == 0 || tw.stop != 0;
-#pragma unroll
-                for (u32 qq = 0; qq + 1 < kQuarters; ++qq) {
-                    cpl[qq * HUFD_DEC_LANES] = 0;
-                }
                 if (reached) {
                     const u32 my_entry = k == 0 ? entry_t : tw.exit;
                     const bool stops_here = tw.stop == k;
-                    lane_count[(u64)c * HUFD_DEC_LANES + ln] = (u16)tw.count[k];
                     fn_out[(u64)my_entry * HUFD_DEC_LANES + ln] =
                         stops_here ? fn_pack(true, 0, tw.count[k] & 0x7FFu) : fn_pack(false, tw.exit, tw.count[k] & 0x7FFu);
-                    cpl[(kQuarters - 1) * HUFD_DEC_LANES] = (u16)((1u << my_entry) | ((stops_here ? kExitStop : tw.exit) << 12));
+                    lane_rec_store(lane_rec, c, ln, lane_rec_pack(0, 0, 0, (1u << my_entry) | ((stops_here ? kExitStop : tw.exit) << 12), tw.count[k]));
                 } else {
-                    lane_count[(u64)c * HUFD_DEC_LANES + ln] = 0;
-                    cpl[(kQuarters - 1) * HUFD_DEC_LANES] = (u16)(kExitStop << 12);
+                    lane_rec_store(lane_rec, c, ln, lane_rec_unreached());
                 }
             }
         }

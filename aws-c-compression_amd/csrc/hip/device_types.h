@@ -236,6 +236,18 @@ struct hufd_emit_rec {
     uint64_t base;    /* chunk_base[c]: the symbols of the item in front of this chunk */
 };
 
+/* one per sub-chunk (lane_rec[chunk][lane]): everything the sync stage hands the emit stage about it, ONE 16-byte store
+ * for the lane that writes it and one 16-byte load for a thread that reads it (five 2-byte values in two arrays laid out
+ * row by row were a memory instruction each) */
+struct __attribute__((aligned(16))) hufd_lane_rec {
+    uint16_t cp[HUFD_DEC_CP_ROWS - 1]; /* where the walk enters the second, third and fourth quarter: [15] usable, [14:11] bits
+                                        * past the quarter boundary, [10:0] symbols from there to the end of the walk */
+    uint16_t merged;                   /* [11:0] entry states whose walk runs into that walk, [15:12] how it leaves: the exit
+                                        * state, kExitStop or kExitNoRef */
+    uint16_t count;                    /* regular chunks: symbols of the true path that start in the sub-chunk (lane 0: from the meeting bit on) */
+    uint16_t reserved[3];              /* zero */
+};
+
 /* Where the items of a plan that is made on the device come from (plan_kernels.hip): the caller's records in DEVICE memory,
  * a stride, what an encode launch left, a packed buffer's offsets or ranges of an indexed stream's blocks (decode) */
 #define HUFD_ITEMS_DEVICE_ARRAY 0u

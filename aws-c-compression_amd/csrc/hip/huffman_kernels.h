@@ -93,7 +93,7 @@ struct hufk_decode_args {
     const void *d_in;
     void *d_out;
     uint16_t *fn_tab;      /* [n_chunks][n_states][HUFD_DEC_LANES] scratch */
-    uint16_t *cp_tab;      /* [n_chunks][HUFD_DEC_CP_ROWS][HUFD_DEC_LANES] scratch: walk checkpoints */
+    struct hufd_lane_rec *lane_rec; /* [n_chunks][HUFD_DEC_LANES] scratch: a sub-chunk's walk checkpoints, merged-state word and symbols */
     uint32_t *chunk_fn;    /* [n_chunks][n_states] scratch */
     uint32_t *slow_list;   /* [n_chunks] scratch: chunks that take the long way through dec_sync */
     uint32_t *emit_list;   /* [n_chunks] scratch: chunks left to dec_emit by dec_emit_fast */
@@ -112,7 +112,6 @@ struct hufk_decode_args {
                               * launch goes without the kernels that only make listed chunks FASTER (dec_sync_guess, _few,
                               * _true, dec_emit_big -- an empty launch is ~4 us each); whatever is listed takes the long way
                               * (dec_sync, dec_emit: exact for every chunk), and the counters say so at the next fetch */
-    uint16_t *lane_count;  /* [n_chunks][HUFD_DEC_LANES] scratch */
     uint8_t *chunk_regular; /* [n_chunks] scratch */
     uint32_t *tail_entry;   /* [n_chunks] scratch: state in which the last whole lane of an end-of-stream chunk leaves */
     uint32_t *chunk_entry; /* [n_chunks] scratch */

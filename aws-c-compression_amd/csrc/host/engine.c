@@ -1682,13 +1682,12 @@ int aws_huffman_amd_encode_plan_results(
     X(d_runs, (cr) * 2 * sizeof(uint32_t))                                                                             \
     X(d_run_fn, (cr) * (ns) * sizeof(uint32_t))                                                                        \
     X(d_fn_tab, (cc) * (ns) * HUFD_DEC_LANES * sizeof(uint16_t))                                                       \
-    X(d_cp_tab, (cc) * HUFD_DEC_CP_ROWS * HUFD_DEC_LANES * sizeof(uint16_t))                                           \
+    X(d_lane_rec, (cc) * HUFD_DEC_LANES * sizeof(struct hufd_lane_rec)) /* (16-byte records: every cut is 256-aligned) */ \
     X(d_chunk_fn, (cc) * (ns) * sizeof(uint32_t))                                                                      \
     X(d_slow_list, ((cc) + 1) * sizeof(uint32_t)) /* [0] count, [1..] chunks */                                        \
     X(d_emit_list, ((cc) + 1) * sizeof(uint32_t))                                                                      \
     X(d_dense_list, ((cc) + 1) * sizeof(uint32_t))                                                                     \
     X(d_counters, HUFK_DEC_COUNTERS * sizeof(uint32_t))                                                                \
-    X(d_lane_count, (cc) * HUFD_DEC_LANES * sizeof(uint16_t))                                                          \
     X(d_chunk_regular, (cc))                                                                                           \
     X(d_tail_entry, (cc) * sizeof(uint32_t))                                                                           \
     X(d_chunk_entry, (cc) * sizeof(uint32_t))                                                                          \
@@ -1700,6 +1699,8 @@ int aws_huffman_amd_encode_plan_results(
      * ONE copy brings both to the host */                                                                             \
     X(d_summary, DEC_SUMMARY_BYTES)                                                                                    \
     X(d_results, (ci) * sizeof(struct hufd_dec_result))
+
+_Static_assert(sizeof(struct hufd_lane_rec) == 16, "a sub-chunk's record is one 16-byte load or store");
 
 static void dec_plan_release_device(struct aws_huffman_amd_decode_plan *p) {
     hufs_free(p->d_arena);
@@ -2644,7 +2645,7 @@ static void dec_plan_launch_args(
     a.d_in = device_input;
     a.d_out = device_output;
     a.fn_tab = p->d_fn_tab;
-    a.cp_tab = p->d_cp_tab;
+    a.lane_rec = p->d_lane_rec;
     a.chunk_fn = p->d_chunk_fn;
     a.slow_list = p->d_slow_list + 1;
     a.emit_list = p->d_emit_list + 1;
@@ -2653,7 +2654,6 @@ static void dec_plan_launch_args(
     a.counters_self_cleared = 1;
     a.summary = p->d_summary;
     a.quiet = p->quiet && !(testing_decode_road() & AWS_HUFFMAN_AMD_TEST_DECODE_ALL_KERNELS);
-    a.lane_count = p->d_lane_count;
     a.chunk_regular = p->d_chunk_regular;
     a.tail_entry = p->d_tail_entry;
     a.chunk_entry = p->d_chunk_entry;

@@ -149,14 +149,13 @@ struct aws_huffman_amd_decode_plan {
     uint32_t *d_runs;      /* per run: item index, run number inside the item */
     uint32_t *d_run_fn;    /* [n_runs][n_states] */
     uint16_t *d_fn_tab;
-    uint16_t *d_cp_tab;
+    struct hufd_lane_rec *d_lane_rec; /* [chunks][HUFD_DEC_LANES]: what the sync stage hands the emit stage per sub-chunk */
     uint32_t *d_chunk_fn;
     uint32_t *d_slow_list; /* [0] how many, [1..] the chunks the regular chunks' kernels left to dec_sync */
     uint32_t *d_emit_list; /* the same for dec_emit_fast / dec_emit */
     uint32_t *d_dense_list; /* [0] how many, [1..] chunks with more symbols than one emit stage */
     uint32_t *d_counters;   /* [HUFK_DEC_COUNTERS] the lists' lengths (hufk_decode_args.counters): clear between launches */
     uint32_t launches_with_chunks; /* (a fetch of results says what the last of them listed: `quiet`) */
-    uint16_t *d_lane_count;
     uint8_t *d_chunk_regular;
     uint32_t *d_tail_entry;
     uint32_t *d_chunk_entry;

@@ -12,7 +12,8 @@ EXTRA=${AB_BENCH_ARGS:-}
 for r in $(seq 1 "$ROUNDS"); do
     for v in "$@"; do
         name=$(basename "$v" .so)
-        timeout 300 python3 bench.py --full --library "$ROOT/$v" --no-cpu-baseline --no-extra-legs --steps "$STEPS" --warmup 5 $EXTRA > "$OUT/${name}_$r.json" 2> "$OUT/${name}_$r.err" || tail -3 "$OUT/${name}_$r.err"
+        # (a run that fails ends the call: nothing more is started on a card that a run may have left in a bad state)
+        timeout -k 10 300 python3 bench.py --full --library "$ROOT/$v" --no-cpu-baseline --no-extra-legs --steps "$STEPS" --warmup 5 $EXTRA > "$OUT/${name}_$r.json" 2> "$OUT/${name}_$r.err" || { st=$?; tail -3 "$OUT/${name}_$r.err"; exit $st; }
     done
 done
 python3 - "$OUT" "$ROUNDS" "$@" <<'PY'

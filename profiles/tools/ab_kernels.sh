@@ -8,7 +8,7 @@ for v in "$@"; do
     name=$(basename "$v" .so)
     OUT=$ROOT/gpurun_out/ab_kernels/$name; mkdir -p "$OUT"
     cd /tmp
-    timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o run -- python3 $ROOT/bench.py --library "$ROOT/$v" --steps 12 --warmup 3 --no-cpu-baseline --no-extra-legs > "$OUT/bench.json" 2> "$OUT/err.txt"
+    timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o run -- python3 $ROOT/bench.py --library "$ROOT/$v" --steps 12 --warmup 3 --no-cpu-baseline --no-extra-legs > "$OUT/bench.json" 2> "$OUT/err.txt" || { st=$?; tail -3 "$OUT/err.txt"; exit $st; }
     cd "$ROOT"
     find "$OUT" -name '*kernel_trace.csv' -delete
     python3 - "$OUT" "$name" <<'PY'
