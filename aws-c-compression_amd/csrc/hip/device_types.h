@@ -259,6 +259,7 @@ struct __attribute__((aligned(16))) hufd_lane_rec {
 #define HUFD_ITEMS_ITEM_BLOCK_RANGES 6u
 #define HUFD_ITEMS_ITEM_SYMBOL_RANGES 7u
 #define HUFD_ITEMS_PACKED_STORED_INPUT 8u
+#define HUFD_ITEMS_PACKED_CONSTANT_INPUT 9u
 /* a range of whole blocks of an indexed stream, as the public header lays it out (struct aws_huffman_amd_block_range) */
 struct hufd_block_range {
     uint64_t first_block;
@@ -332,6 +333,12 @@ struct hufd_item_source {
      * -- is its bytes as they lie: in_off = where they start, in_len = 0 (nothing for the decode kernels), out_cap = their
      * number; the index entries of such an item are not read.  A named item's flag above 1: no plan */
     const uint8_t *packed_stored;
+    /* a packed input with constant items as well (decode, huffman_amd_constant.h): packed_stored[i] is the item's kind, 2 for
+     * an item whose 9 packed bytes at packed_bytes + packed_offsets[i] are its symbols' number, little-endian, and the byte
+     * they all are -- nothing for the decode kernels either: the plan fills it.  No plan: a kind above 2, an offset of 2^63 or
+     * more, a constant item whose packed length is not 9, a number of 9 or less or above 2^32 (the head is read only where the
+     * kind and the length say there is one) */
+    const uint8_t *packed_bytes;
 };
 
 /*

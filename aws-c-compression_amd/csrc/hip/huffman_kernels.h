@@ -296,9 +296,31 @@ int hufk_pack_offsets_stored(
 int hufk_stored_copy_encode(
     const struct hufd_enc_item *items, uint32_t n_items, const struct hufd_enc_seg *segs, uint32_t n_segs, const uint32_t *solo,
     uint32_t n_solo, const uint32_t *tiny, uint32_t n_tiny, const uint8_t *stored, const uint64_t *offsets, uint64_t capacity,
-    const void *input, void *output, struct hufd_enc_result *results, uint64_t *counts, void *stream);
+    const void *input, void *output, struct hufd_enc_result *results, uint64_t *counts, uint8_t *differs, void *stream);
 int hufk_stored_records(
-    const uint64_t *offsets, const uint64_t *lengths, const uint8_t *stored, uint32_t n_items, uint64_t *stored_rec, void *stream);
+    const uint64_t *offsets, const uint64_t *lengths, const uint8_t *stored, const void *packed, uint32_t n_items,
+    uint64_t *stored_rec, void *stream);
+/* Constant items (huffman_amd_constant.h; the same bodies).
+ *   _constant_detect        in front of the scan, distributed by the plan's lists as the copy is: differs[i] = 1 where a byte
+ *                           of item i is not its first byte (items with carried bits or of 9 bytes or fewer are not read);
+ *                           differs[] must be clear in front, and the copy clears it again
+ *   _pack_offsets_constant  hufk_pack_offsets_stored with the constant rule in front: kinds[i] = 0 / 1 / 2, len_i = 9 for a
+ *                           constant item, summary[2 .. 5] = 0 (summary: six words)
+ *   _stored_copy_encode     with differs != NULL: stored[] holds kinds; also the 9 bytes of every constant item that fits
+ *                           whole, its record, counts[2] += the constant items, counts[3] += their bytes, differs[] cleared
+ *   _stored_records         with packed != NULL: stored[] holds kinds, and a constant item's record is {HUFK_CONSTANT | value,
+ *                           count}, read from its head at packed + offsets[i] (checked by the planner's pass in front)
+ *   _stored_copy_decode     fills such an item where it would copy */
+#define HUFK_CONSTANT (1ull << 63)
+#define HUFK_CONSTANT_BYTES 9u
+#define HUFK_CONSTANT_MAX_COUNT 0x100000000ull
+int hufk_constant_detect(
+    const struct hufd_enc_item *items, uint32_t n_items, const struct hufd_enc_seg *segs, uint32_t n_segs, const uint32_t *solo,
+    uint32_t n_solo, const uint32_t *tiny, uint32_t n_tiny, const void *input, uint8_t *differs, void *stream);
+int hufk_pack_offsets_constant(
+    const struct hufd_enc_item *items, const struct hufd_enc_result *lengths, uint32_t n_items, uint32_t tile_items, uint64_t align,
+    uint64_t capacity, uint64_t *tile_sums, uint64_t *offsets, struct hufd_enc_item *packed, uint64_t *summary, uint8_t *kinds,
+    const uint8_t *differs, void *stream);
 /* ... of a plan of ranges of an indexed batch (huffman_amd_stored_index.h): stored_rec[r] = {items[r].in_off, items[r].out_cap}
  * for a range of bytes in an item flagged 1, {.., HUFK_NOT_STORED} for any other; ranges: four words each, the first the item */
 int hufk_stored_range_records(

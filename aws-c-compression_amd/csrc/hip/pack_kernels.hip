@@ -137,6 +137,14 @@ constexpr u32 kPackStoredTiles = 8;
  * bodies with both constants, INDEXED and STORED == kPackStored.  `lengths` and batch.second are both the plan's item records.
  * Where the index does not fit every coded length is 0, so no item is stored and every flag is 0. */
 constexpr u32 kPackStoredIndexed = 9;
+/* An eleventh, the offsets of aws_huffman_amd_encode_plan_launch_packed_constant (huffman_amd_constant.h): kPackStored with one
+ * rule in front,
+ *   constant_i = ovf_bits_i == 0 && in_len_i > 9 && ceil(total_bits_i / 8) > 9 && !differs[i],   len_i = 9 for such an item
+ * -- differs[]: what the detection (stored_copy.hpp) left in front of the scan --; the flag it writes is the item's kind, 0, 1
+ * or 2, a constant item gets no room in the second record array either, and four words are cleared for the copy's counts.
+ * Builds of the bodies of its own again (STORED == kPackConstant). */
+constexpr u32 kPackConstant = 10;
+constexpr u64 kPackConstantBytes = 9; /* AWS_HUFFMAN_AMD_CONSTANT_BYTES */
 constexpr u64 kPackNotStored = HUFK_NOT_STORED;
 
 struct pack_batch {
@@ -148,12 +156,21 @@ struct pack_batch {
     const u64 *directory; /* kPackIndexed: [n_items + 1][2], and `index` scanned, `capacity` its entries;
                            * kPackUnstored, kPackStoredTiles: the plan's stored records, [n_items][2] */
     const void *second;   /* kPackStored, kPackUnstored: the plan's item records (what `lengths` is not) */
-    u8 *stored;           /* kPackStored: the caller's flags */
+    u8 *stored;           /* kPackStored: the caller's flags; kPackConstant: the caller's kinds */
+    const u8 *differs;    /* kPackConstant: the detection's marks */
 };
 
 /* the rule of huffman_amd_stored.h: a tie is stored, carried bits and empty items never */
 __device__ __forceinline__ bool pack_item_stored(const hufd_enc_item *item, u64 coded_len) {
     return item->in_len > 0 && item->ovf_bits == 0 && coded_len >= item->in_len;
+}
+
+/* the rule of huffman_amd_constant.h in front of it: 2 constant, 1 stored, 0 coded */
+__device__ __forceinline__ u32 pack_item_kind(const hufd_enc_item *item, u64 coded_len, u32 differs) {
+    if (item->ovf_bits == 0 && item->in_len > kPackConstantBytes && coded_len > kPackConstantBytes && !differs) {
+        return 2u;
+    }
+    return pack_item_stored(item, coded_len) ? 1u : 0u;
 }
 
 /* whether a batch of `blocks` blocks has an index in `capacity` entries (blocks + 1 of them, blocks below 2^32) */
@@ -183,6 +200,12 @@ __device__ __forceinline__ u64 pack_length(const void *lengths, u32 decode, u64 
         const hufd_enc_item *item = reinterpret_cast<const hufd_enc_item *>(batch.second) + i;
         const u64 coded = pack_coded_length<INDEXED>(lengths, item, i, batch);
         return pack_item_stored(item, coded) ? item->in_len : coded;
+    }
+    if (STORED == kPackConstant) {
+        const hufd_enc_item *item = reinterpret_cast<const hufd_enc_item *>(batch.second) + i;
+        const u64 coded = pack_coded_length<INDEXED>(lengths, item, i, batch);
+        const u32 kind = pack_item_kind(item, coded, batch.differs[i]);
+        return kind == 2u ? kPackConstantBytes : (kind ? item->in_len : coded);
     }
     if (STORED == kPackUnstored) {
         const u64 raw = batch.directory[2 * i + 1];
@@ -348,6 +371,15 @@ __device__ __forceinline__ void pack_offsets_body(
                     to->out_cap = 0;
                 }
                 batch.stored[i] = stored ? 1u : 0u;
+            } else if (STORED == kPackConstant) {
+                const pack_encode::item *from = reinterpret_cast<const pack_encode::item *>(batch.second) + i;
+                pack_encode::item *to = reinterpret_cast<pack_encode::item *>(packed) + i;
+                const u32 kind = pack_item_kind(from, pack_coded_length<INDEXED>(lengths, from, i, batch), batch.differs[i]);
+                pack_encode::place(from, to, off, 0, reserved, capacity);
+                if (kind) {
+                    to->out_cap = 0;
+                }
+                batch.stored[i] = (u8)kind;
             } else if (STORED == kPackUnstored) {
                 pack_decode::place(
                     reinterpret_cast<const pack_decode::item *>(batch.second) + i, reinterpret_cast<pack_decode::item *>(packed) + i, off,
@@ -405,6 +437,12 @@ __device__ __forceinline__ void pack_offsets_body(
                 if (STORED == kPackStored) { /* (the stored items and their bytes: the copy behind the encode pass adds them) */
                     summary[2] = 0;
                     summary[3] = 0;
+                }
+                if (STORED == kPackConstant) { /* (... and the constant items and theirs) */
+                    summary[2] = 0;
+                    summary[3] = 0;
+                    summary[4] = 0;
+                    summary[5] = 0;
                 }
             }
         }
@@ -469,6 +507,9 @@ __global__ __launch_bounds__(kPackThreads) void unpack_records_kernel(
         } else if (scan.decode == kPackStored) {
             pack_tile_sums_body<true, false, kPackStored>(
                 scan.lengths, kPackStored, scan.n_items, scan.tile_items, scan.align_mask, scan.tile_sums, scan.batch);
+        } else if (scan.decode == kPackConstant) {
+            pack_tile_sums_body<true, false, kPackConstant>(
+                scan.lengths, kPackConstant, scan.n_items, scan.tile_items, scan.align_mask, scan.tile_sums, scan.batch);
         } else if (scan.decode == kPackStoredIndexed) {
             pack_tile_sums_body<true, true, kPackStored>(
                 scan.lengths, kPackStoredIndexed, scan.n_items, scan.tile_items, scan.align_mask, scan.tile_sums, scan.batch);
@@ -488,6 +529,10 @@ __global__ __launch_bounds__(kPackThreads) void unpack_records_kernel(
         } else if (scan.decode == kPackStored) {
             pack_offsets_body<true, false, kPackStored>(
                 scan.batch.second, scan.lengths, kPackStored, scan.n_items, scan.tile_items, scan.align_mask, scan.out_capacity,
+                scan.tile_sums, scan.offsets, scan.packed, scan.summary, scan.batch);
+        } else if (scan.decode == kPackConstant) {
+            pack_offsets_body<true, false, kPackConstant>(
+                scan.batch.second, scan.lengths, kPackConstant, scan.n_items, scan.tile_items, scan.align_mask, scan.out_capacity,
                 scan.tile_sums, scan.offsets, scan.packed, scan.summary, scan.batch);
         } else if (scan.decode == kPackStoredIndexed) {
             pack_offsets_body<true, true, kPackStored>(
@@ -672,6 +717,21 @@ int hufk_pack_offsets_stored(
         lengths, kPackStored, n_items, tile_items, tile_sums, offsets, summary, batch, (hipStream_t)stream, align, capacity, packed);
 }
 
+int hufk_pack_offsets_constant(
+    const struct hufd_enc_item *items, const struct hufd_enc_result *lengths, uint32_t n_items, uint32_t tile_items, uint64_t align,
+    uint64_t capacity, uint64_t *tile_sums, uint64_t *offsets, struct hufd_enc_item *packed, uint64_t *summary, uint8_t *kinds,
+    const uint8_t *differs, void *stream) {
+    if (n_items == 0 || tile_items == 0) {
+        return 0;
+    }
+    pack_batch batch{};
+    batch.second = items;
+    batch.stored = kinds;
+    batch.differs = differs;
+    return pack_batch_launch(
+        lengths, kPackConstant, n_items, tile_items, tile_sums, offsets, summary, batch, (hipStream_t)stream, align, capacity, packed);
+}
+
 int hufk_pack_offsets_stored_indexed(
     const struct hufd_enc_item *items, uint32_t n_items, uint32_t tile_items, uint64_t align, uint64_t capacity,
     const uint64_t *directory, const uint64_t *index, uint64_t index_capacity, uint64_t *tile_sums, uint64_t *offsets,
@@ -741,7 +801,7 @@ int hufk_unpack_offsets(
 int hufk_stored_copy_encode(
     const struct hufd_enc_item *items, uint32_t n_items, const struct hufd_enc_seg *segs, uint32_t n_segs, const uint32_t *solo,
     uint32_t n_solo, const uint32_t *tiny, uint32_t n_tiny, const uint8_t *stored, const uint64_t *offsets, uint64_t capacity,
-    const void *input, void *output, struct hufd_enc_result *results, uint64_t *counts, void *stream) {
+    const void *input, void *output, struct hufd_enc_result *results, uint64_t *counts, uint8_t *differs, void *stream) {
     if (n_items == 0) {
         return 0;
     }
@@ -768,7 +828,34 @@ int hufk_stored_copy_encode(
     job.capacity = capacity;
     job.enc_results = results;
     job.counts = counts;
+    job.differs = differs;
     job.item_blocks = item_blocks;
+    stored_launch(job, (u32)blocks, (hipStream_t)stream);
+    return (int)hipGetLastError();
+}
+
+int hufk_constant_detect(
+    const struct hufd_enc_item *items, uint32_t n_items, const struct hufd_enc_seg *segs, uint32_t n_segs, const uint32_t *solo,
+    uint32_t n_solo, const uint32_t *tiny, uint32_t n_tiny, const void *input, uint8_t *differs, void *stream) {
+    const u64 blocks = (u64)n_segs + ((u64)n_solo + kStoredWaves - 1) / kStoredWaves + ((u64)n_tiny + kStoredThreads - 1) / kStoredThreads;
+    if (n_items == 0 || blocks == 0) {
+        return 0;
+    }
+    if (blocks >> 31) {
+        return (int)hipErrorInvalidValue;
+    }
+    stored_job job{};
+    job.in = (const u8 *)input;
+    job.n_items = n_items;
+    job.receiver = 4;
+    job.items = items;
+    job.segs = segs;
+    job.solo = solo;
+    job.tiny = tiny;
+    job.n_segs = n_segs;
+    job.n_solo = n_solo;
+    job.n_tiny = n_tiny;
+    job.differs = differs;
     stored_launch(job, (u32)blocks, (hipStream_t)stream);
     return (int)hipGetLastError();
 }
@@ -778,6 +865,9 @@ int hufk_stored_copy_decode(
     struct hufd_dec_result *results, const void *input, void *output, void *stream) {
     if (n_items == 0) {
         return 0;
+    }
+    if (!output) { /* (a size query places no item: no workgroup for a tile -- a constant item may count 2^18 of them) */
+        n_tiles = 0;
     }
     const u64 blocks = n_tiles + ((u64)n_items + kStoredWaves - 1) / kStoredWaves + ((u64)n_items + kStoredThreads - 1) / kStoredThreads;
     if (n_tiles >> 31 || blocks >> 31) {
@@ -825,11 +915,13 @@ int hufk_planes_merge(
 }
 
 int hufk_stored_records(
-    const uint64_t *offsets, const uint64_t *lengths, const uint8_t *stored, uint32_t n_items, uint64_t *stored_rec, void *stream) {
+    const uint64_t *offsets, const uint64_t *lengths, const uint8_t *stored, const void *packed, uint32_t n_items,
+    uint64_t *stored_rec, void *stream) {
     if (n_items == 0) {
         return 0;
     }
     stored_job job{};
+    job.in = (const u8 *)packed;
     job.n_items = n_items;
     job.receiver = 2;
     job.offsets = offsets;

@@ -68,7 +68,8 @@ __device__ __forceinline__ raw_item load_item(const hufd_item_source &src, u32 i
         r.out_off = e.in_off;
         r.out_cap = e.in_len;
         r.bits = 0;
-    } else if (!ENC && (src.kind == HUFD_ITEMS_PACKED_INPUT || src.kind == HUFD_ITEMS_PACKED_STORED_INPUT)) {
+    } else if (!ENC && (src.kind == HUFD_ITEMS_PACKED_INPUT || src.kind == HUFD_ITEMS_PACKED_STORED_INPUT ||
+                        src.kind == HUFD_ITEMS_PACKED_CONSTANT_INPUT)) {
         /* item i of a packed buffer: from its offset to the next one, or as long as the sender says -- or, flagged as stored
          * raw, nothing for the decode kernels (a flag that is neither 0 nor 1: no plan) */
         const u64 at = src.packed_offsets[i];
@@ -85,6 +86,21 @@ __device__ __forceinline__ raw_item load_item(const hufd_item_source &src, u32 i
             const u32 flag = src.packed_stored[i];
             r.in_len = flag ? 0 : r.in_len;
             r.bad |= flag > 1u ? 1u : 0u;
+        }
+        if (src.kind == HUFD_ITEMS_PACKED_CONSTANT_INPUT) {
+            /* the item's kind; a constant item is its head of 9 bytes, read where the kind and the length say there is one */
+            const u32 kind = src.packed_stored[i];
+            r.bad |= (kind > 2u || (at >> 63)) ? 1u : 0u;
+            if (kind == 2u && !r.bad) {
+                u64 count = 0;
+                if (r.in_len == HUFK_CONSTANT_BYTES) {
+                    for (u32 k = 0; k < 8; ++k) {
+                        count |= (u64)src.packed_bytes[at + k] << (8 * k);
+                    }
+                }
+                r.bad |= (count <= HUFK_CONSTANT_BYTES || count > HUFK_CONSTANT_MAX_COUNT) ? 1u : 0u;
+            }
+            r.in_len = kind ? 0 : r.in_len;
         }
         r.out_off = 0;
         r.out_cap = 0;

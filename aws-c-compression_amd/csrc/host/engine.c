@@ -18,6 +18,7 @@
 #include <aws/compression/huffman_amd_planes.h>
 #include <aws/compression/huffman_amd_planes_delta.h>
 #include <aws/compression/huffman_amd_ranges.h>
+#include <aws/compression/huffman_amd_constant.h>
 #include <aws/compression/huffman_amd_stored.h>
 #include <aws/compression/huffman_amd_stored_index.h>
 
@@ -862,7 +863,7 @@ static int enc_plan_fill(
     p->largest_out_cap = stats.largest_out_cap;
     p->most_overflow_bits = stats.worst_bits;
     p->longest_in_len = stats.longest;
-    p->packed = p->packed_sized = p->stored = false;
+    p->packed = p->packed_sized = p->stored = p->constant = false;
     p->block_indexed = false;
     if (n_items >= PLAN_ON_DEVICE_MIN_ITEMS && n_items < 0xFFFFFFFFull && stats.shortest >= 1 && stats.longest <= tiny_limit &&
         stats.worst_bits <= 32) {
@@ -1089,7 +1090,7 @@ static int enc_plan_fill_on_device(struct aws_huffman_amd_encode_plan *p, const 
     p->largest_out_cap = 0;
     p->most_overflow_bits = 0;
     p->longest_in_len = 0;
-    p->packed = p->packed_sized = p->stored = false;
+    p->packed = p->packed_sized = p->stored = p->constant = false;
     p->block_indexed = false;
     if (n_items == 0) {
         return AWS_OP_SUCCESS;
@@ -1253,7 +1254,7 @@ static int enc_plan_launch_items(
     p->last_input = device_input;
     p->last_output = device_output;
     if (!length_only) {
-        p->stored = false; /* (a stored launch says so behind its encode pass) */
+        p->stored = p->constant = false; /* (a stored launch says so behind its encode pass) */
     }
     p->launched = !length_only; /* (a length query leaves lengths in the records and no output: nothing to chain a decode to) */
     p->last_single_pass =
@@ -1307,7 +1308,9 @@ static int enc_plan_reserve_packed(struct aws_huffman_amd_encode_plan *p, size_t
     const struct arena_part parts[] = {
         {&p->d_packed_items, ci * sizeof(struct hufd_enc_item)},
         {&p->d_pack_tile_sums, 2 * n_tiles * sizeof(uint64_t)},
-        {&p->d_pack_summary, 4 * sizeof(uint64_t)}}; /* (the last two: a stored launch's counts) */
+        {&p->d_pack_summary, 6 * sizeof(uint64_t)}, /* (the last four: a stored launch's counts, a constant launch's) */
+        {&p->d_pack_differs, ci}};
+    p->pack_differs_clear = false;
     if (arena_alloc(&p->d_packed_arena, ARENA_PARTS(parts))) {
         return 2;
     }
@@ -1347,12 +1350,17 @@ static int enc_plan_launch_stored_copy(
     uint64_t output_capacity,
     const uint64_t *device_offsets,
     const uint8_t *device_stored,
+    bool constant, /* device_stored holds kinds: the 9 bytes and the records of the constant items, and the detection's marks cleared */
     void *stream) {
 
     ON_DEVICE(p->engine->device);
     int e = hufk_stored_copy_encode(
         p->d_items, p->n_items, p->d_segs, p->n_segs, p->d_solo, p->n_solo, p->d_tiny, p->n_tiny, device_stored, device_offsets,
-        output_capacity, device_input, device_output, p->d_results, p->d_pack_summary + 2, stream ? stream : p->engine->stream);
+        output_capacity, device_input, device_output, p->d_results, p->d_pack_summary + 2, constant ? p->d_pack_differs : NULL,
+        stream ? stream : p->engine->stream);
+    if (constant) {
+        p->pack_differs_clear = !e;
+    }
     if (!e) {
         e = plan_mark_done(&p->done_event, &p->done_on_engine_stream, p->engine, stream);
     }
@@ -1363,6 +1371,7 @@ static int enc_plan_launch_stored_copy(
         return raise_hip(e);
     }
     p->stored = true;
+    p->constant = constant;
     return AWS_OP_SUCCESS;
 }
 
@@ -1371,7 +1380,8 @@ static int enc_plan_launch_stored_copy(
  *   - the lengths: a length pass into the plan's result records, or (ix) the batch's block index, whose hot pass reads the
  *     symbols once and leaves the coded lengths in the index;
  *   - the scan: the offsets and the second record array from those lengths; with `device_stored` it also decides which items
- *     are stored raw, flags them and gives them no room in the second record array;
+ *     are stored raw, flags them and gives them no room in the second record array; `constant` (huffman_amd_constant.h): the
+ *     detection of constant items runs in front of the scan, whose flags are then kinds;
  *   - the encode pass over that array (its records replace the lengths), and behind it the copy of the stored items.
  */
 static int enc_plan_launch_packed_any(
@@ -1382,6 +1392,7 @@ static int enc_plan_launch_packed_any(
     uint64_t *device_offsets,
     uint32_t align,
     uint8_t *device_stored, /* NULL: no item is stored */
+    bool constant, /* (with device_stored, without ix) */
     const struct enc_plan_index_args *ix, /* NULL: no index is made */
     void *stream) {
 
@@ -1413,12 +1424,29 @@ static int enc_plan_launch_packed_any(
         p->packed = false;
         p->packed_sized = true;
         p->stored = device_stored != NULL;
+        p->constant = constant;
         /* (the index read the plan's records and scratch on this stream: whoever gets its arrays next waits, as for a launch) */
         e = ix ? plan_mark_done(&p->done_event, &p->done_on_engine_stream, p->engine, stream) : 0;
         return e ? raise_hip(e) : AWS_OP_SUCCESS;
     }
     const uint64_t *directory = ix ? (const uint64_t *)ix->directory : NULL;
+    if (constant) {
+        /* the marks: clear from the launch in front, or cleared here (a fresh array, a launch that failed half way) */
+        int e = p->pack_differs_clear ? 0 : hufs_memset(p->d_pack_differs, 0, p->cap_packed_items, st);
+        p->pack_differs_clear = false; /* (until the copy behind the encode pass has been queued) */
+        if (!e) {
+            e = hufk_constant_detect(
+                p->d_items, p->n_items, p->d_segs, p->n_segs, p->d_solo, p->n_solo, p->d_tiny, p->n_tiny, device_input,
+                p->d_pack_differs, st);
+        }
+        if (e) {
+            return raise_hip(e);
+        }
+    }
     const int e =
+        constant ? hufk_pack_offsets_constant(
+                       p->d_items, p->d_results, p->n_items, tile_items, align, output_capacity, p->d_pack_tile_sums, device_offsets,
+                       p->d_packed_items, p->d_pack_summary, device_stored, p->d_pack_differs, st) :
         ix ? (device_stored ? hufk_pack_offsets_stored_indexed(
                                   p->d_items, p->n_items, tile_items, align, output_capacity, directory, ix->index, ix->index_capacity,
                                   p->d_pack_tile_sums, device_offsets, p->d_packed_items, p->d_pack_summary, device_stored, st)
@@ -1442,7 +1470,7 @@ static int enc_plan_launch_packed_any(
     if (!device_stored) {
         return AWS_OP_SUCCESS;
     }
-    return enc_plan_launch_stored_copy(p, device_input, device_output, output_capacity, device_offsets, device_stored, stream);
+    return enc_plan_launch_stored_copy(p, device_input, device_output, output_capacity, device_offsets, device_stored, constant, stream);
 }
 
 int aws_huffman_amd_encode_plan_launch_packed(
@@ -1457,7 +1485,23 @@ int aws_huffman_amd_encode_plan_launch_packed(
     if (!packed_launch_args_ok(p, device_output, output_capacity, device_offsets, align)) {
         return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
     }
-    return enc_plan_launch_packed_any(p, device_input, device_output, output_capacity, device_offsets, align, NULL, NULL, stream);
+    return enc_plan_launch_packed_any(p, device_input, device_output, output_capacity, device_offsets, align, NULL, false, NULL, stream);
+}
+
+int aws_huffman_amd_encode_plan_launch_packed_constant(
+    struct aws_huffman_amd_encode_plan *p,
+    const void *device_input,
+    void *device_output,
+    uint64_t output_capacity,
+    uint64_t *device_offsets,
+    uint8_t *device_kinds,
+    uint32_t align,
+    void *stream) {
+
+    if (!packed_launch_args_ok(p, device_output, output_capacity, device_offsets, align) || !device_kinds) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    return enc_plan_launch_packed_any(p, device_input, device_output, output_capacity, device_offsets, align, device_kinds, true, NULL, stream);
 }
 
 int aws_huffman_amd_encode_plan_launch_packed_stored(
@@ -1473,7 +1517,7 @@ int aws_huffman_amd_encode_plan_launch_packed_stored(
     if (!packed_launch_args_ok(p, device_output, output_capacity, device_offsets, align) || !device_stored) {
         return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
     }
-    return enc_plan_launch_packed_any(p, device_input, device_output, output_capacity, device_offsets, align, device_stored, NULL, stream);
+    return enc_plan_launch_packed_any(p, device_input, device_output, output_capacity, device_offsets, align, device_stored, false, NULL, stream);
 }
 
 int aws_huffman_amd_encode_plan_launch_packed_indexed(
@@ -1498,7 +1542,7 @@ int aws_huffman_amd_encode_plan_launch_packed_indexed(
         !enc_plan_block_index_args_ok(p, device_input, &ix)) {
         return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
     }
-    return enc_plan_launch_packed_any(p, device_input, device_output, output_capacity, device_offsets, align, NULL, &ix, stream);
+    return enc_plan_launch_packed_any(p, device_input, device_output, output_capacity, device_offsets, align, NULL, false, &ix, stream);
 }
 
 int aws_huffman_amd_encode_plan_launch_packed_stored_indexed(
@@ -1524,7 +1568,7 @@ int aws_huffman_amd_encode_plan_launch_packed_stored_indexed(
         !enc_plan_block_index_args_ok(p, device_input, &ix)) {
         return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
     }
-    return enc_plan_launch_packed_any(p, device_input, device_output, output_capacity, device_offsets, align, device_stored, &ix, stream);
+    return enc_plan_launch_packed_any(p, device_input, device_output, output_capacity, device_offsets, align, device_stored, false, &ix, stream);
 }
 
 int aws_huffman_amd_encode_plan_stored_size(
@@ -1545,6 +1589,28 @@ int aws_huffman_amd_encode_plan_stored_size(
     }
     if (stored_bytes) {
         *stored_bytes = counts[1];
+    }
+    return AWS_OP_SUCCESS;
+}
+
+int aws_huffman_amd_encode_plan_constant_size(
+    struct aws_huffman_amd_encode_plan *p,
+    uint64_t *constant_items,
+    uint64_t *constant_bytes,
+    void *stream) {
+
+    if (!p || !p->packed_sized || !p->constant) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    uint64_t counts[2] = {0, 0};
+    if (plan_read_words(p->engine->device, p->n_items ? p->d_pack_summary + 4 : NULL, counts, 2, stream ? stream : p->engine->stream)) {
+        return AWS_OP_ERR;
+    }
+    if (constant_items) {
+        *constant_items = counts[0];
+    }
+    if (constant_bytes) {
+        *constant_bytes = counts[1];
     }
     return AWS_OP_SUCCESS;
 }
@@ -2196,9 +2262,11 @@ static int dec_items_to_host(
         if (!e) {
             e = hufs_stream_sync(st);
         }
-    } else if (src->kind == HUFD_ITEMS_PACKED_INPUT || src->kind == HUFD_ITEMS_PACKED_STORED_INPUT) {
+    } else if (src->kind == HUFD_ITEMS_PACKED_INPUT || src->kind == HUFD_ITEMS_PACKED_STORED_INPUT ||
+               src->kind == HUFD_ITEMS_PACKED_CONSTANT_INPUT) {
         const size_t n_offsets = src->packed_lengths ? n_items : n_items + 1;
-        const bool flagged = src->kind == HUFD_ITEMS_PACKED_STORED_INPUT;
+        const bool kinds = src->kind == HUFD_ITEMS_PACKED_CONSTANT_INPUT;
+        const bool flagged = src->kind == HUFD_ITEMS_PACKED_STORED_INPUT || kinds;
         uint64_t *at = malloc((n_offsets ? n_offsets : 1) * sizeof(*at));
         uint64_t *len = malloc((n_items ? n_items : 1) * sizeof(*len));
         uint8_t *flag = calloc(n_items ? n_items : 1, 1);
@@ -2217,10 +2285,30 @@ static int dec_items_to_host(
         }
         for (size_t i = 0; i < n_items && !e; ++i) {
             /* (offsets that decrease: a length no plan takes, as the device planner's `invalid`) */
-            const bool bad = (src->packed_lengths ? (i > 0 && at[i - 1] > at[i]) : at[i + 1] < at[i]) || flag[i] > 1;
+            bool bad = (src->packed_lengths ? (i > 0 && at[i - 1] > at[i]) : at[i + 1] < at[i]) || flag[i] > (kinds ? 2 : 1);
+            const uint64_t bytes = bad ? 0 : (src->packed_lengths ? len[i] : at[i + 1] - at[i]);
+            if (kinds && !bad) {
+                /* (load_item of plan_kernels.hip is the rule this restates: the head of a constant item, read where the kind
+                 * and the length say there is one -- eight bytes at a time: only coders whose plans the host lays out come here) */
+                bad = at[i] >> 63;
+                if (flag[i] == 2 && !bad) {
+                    uint64_t count = 0;
+                    if (bytes == HUFK_CONSTANT_BYTES) {
+                        uint8_t head[8];
+                        e = hufs_copy_d2h(head, src->packed_bytes + at[i], sizeof(head), st);
+                        if (!e) {
+                            e = hufs_stream_sync(st);
+                        }
+                        for (size_t k = 0; k < 8 && !e; ++k) {
+                            count |= (uint64_t)head[k] << (8 * k);
+                        }
+                    }
+                    bad = count <= HUFK_CONSTANT_BYTES || count > HUFK_CONSTANT_MAX_COUNT;
+                }
+            }
             items[i].in_offset = at[i];
-            /* (an item stored raw: nothing for the decode kernels) */
-            items[i].in_len = bad ? UINT64_MAX : (flag[i] ? 0 : (src->packed_lengths ? len[i] : at[i + 1] - at[i]));
+            /* (an item stored raw, or a constant one: nothing for the decode kernels) */
+            items[i].in_len = bad ? UINT64_MAX : (flag[i] ? 0 : bytes);
         }
         free(at);
         free(len);
@@ -2880,6 +2968,7 @@ static int dec_plan_stored_records(
     const uint64_t *device_lengths,
     const uint8_t *device_stored,
     const void *device_ranges,
+    const void *device_packed, /* != NULL: device_stored holds kinds, and a constant item's record comes from its head (huffman_amd_constant.h) */
     void *stream) {
 
     void *st = stream ? stream : p->engine->stream;
@@ -2890,7 +2979,7 @@ static int dec_plan_stored_records(
     if (!e) {
         e = device_ranges
                 ? hufk_stored_range_records((const uint64_t *)device_ranges, device_stored, p->d_items, p->n_items, p->d_stored_rec, st)
-                : hufk_stored_records(device_offsets, device_lengths, device_stored, p->n_items, p->d_stored_rec, st);
+                : hufk_stored_records(device_offsets, device_lengths, device_stored, device_packed, p->n_items, p->d_stored_rec, st);
     }
     if (!e) {
         e = hufk_stored_tiles(
@@ -2946,7 +3035,50 @@ int aws_huffman_amd_decode_plan_reset_packed_stored_input(
     if (p->n_items == 0) {
         return AWS_OP_SUCCESS;
     }
-    if (dec_plan_stored_records(p, device_offsets, device_lengths, device_stored, NULL, stream)) {
+    if (dec_plan_stored_records(p, device_offsets, device_lengths, device_stored, NULL, NULL, stream)) {
+        return AWS_OP_ERR;
+    }
+    p->stored = true;
+    return AWS_OP_SUCCESS;
+}
+
+int aws_huffman_amd_decode_plan_reset_packed_constant_input(
+    struct aws_huffman_amd_decode_plan *p,
+    const void *device_packed,
+    const uint64_t *device_offsets,
+    const uint64_t *device_lengths,
+    const uint8_t *device_kinds,
+    size_t item_count,
+    void *stream) {
+
+    if (!device_kinds) {
+        return aws_huffman_amd_decode_plan_reset_packed_input(p, device_offsets, device_lengths, item_count, stream);
+    }
+    if (!p) {
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    if ((!device_offsets && item_count) || (!device_packed && item_count) || ((uintptr_t)device_offsets & 7u) ||
+        ((uintptr_t)device_lengths & 7u)) {
+        p->quiet = false; /* (as a refused aws_huffman_amd_decode_plan_reset_packed_input) */
+        p->launches_with_chunks = 0;
+        return aws_raise_error(AWS_ERROR_INVALID_ARGUMENT);
+    }
+    struct hufd_item_source src;
+    memset(&src, 0, sizeof(src));
+    src.kind = HUFD_ITEMS_PACKED_CONSTANT_INPUT;
+    src.packed_offsets = device_offsets;
+    src.packed_lengths = device_lengths;
+    src.packed_stored = device_kinds;
+    src.packed_bytes = (const uint8_t *)device_packed;
+    /* the planner's pass checks every offset, length, kind and head; a stored or constant item comes out of it without encoded
+     * bytes, and the records of the copy -- for a constant item {its value, its count} -- are made behind it */
+    if (dec_plan_fill_on_device(p, &src, item_count, stream)) {
+        return AWS_OP_ERR;
+    }
+    if (p->n_items == 0) {
+        return AWS_OP_SUCCESS;
+    }
+    if (dec_plan_stored_records(p, device_offsets, device_lengths, device_kinds, NULL, device_packed, stream)) {
         return AWS_OP_ERR;
     }
     p->stored = true;
@@ -3204,7 +3336,7 @@ static int dec_plan_stored_ranges(struct aws_huffman_amd_decode_plan *p, const u
     if (!device_stored || p->n_items == 0) {
         return AWS_OP_SUCCESS;
     }
-    if (dec_plan_stored_records(p, NULL, NULL, device_stored, device_ranges, stream)) {
+    if (dec_plan_stored_records(p, NULL, NULL, device_stored, device_ranges, NULL, stream)) {
         return AWS_OP_ERR;
     }
     p->stored_ranges = true;

@@ -114,12 +114,18 @@ struct aws_huffman_amd_encode_plan {
     void *d_packed_arena;
     struct hufd_enc_item *d_packed_items; /* [cap_packed_items] */
     uint64_t *d_pack_tile_sums;           /* [2 * cap_pack_tiles] */
-    uint64_t *d_pack_summary;             /* [4]: the total, the largest reserved length; of a stored launch: the stored items, their bytes */
+    uint64_t *d_pack_summary;             /* [6]: the total, the largest reserved length; of a stored launch: the stored items, their
+                                           * bytes; of a constant launch: also the constant items, their bytes */
+    uint8_t *d_pack_differs;              /* [cap_packed_items]: the marks of a constant launch's detection (huffman_amd_constant.h) */
+    bool pack_differs_clear;              /* ... are all 0: every such launch leaves them so behind itself; a fresh array, or a
+                                           * launch that was not queued whole, is cleared in front of the next */
     size_t cap_packed_items, cap_pack_tiles;
     bool packed;       /* the last encode launch was a packed one: its output lies where d_packed_items say */
     bool packed_sized; /* ... and one was made since the plan was filled: d_pack_summary is of these items */
     bool stored;       /* the last encode launch was aws_huffman_amd_encode_plan_launch_packed_stored (huffman_amd_stored.h): raw
                         * items lie among the coded ones, and d_pack_summary[2], [3] count them */
+    bool constant;     /* ... was aws_huffman_amd_encode_plan_launch_packed_constant (then `stored` as well): d_pack_summary[4], [5]
+                        * count the constant items */
     /* aws_huffman_amd_encode_plan_block_index (huffman_amd_batch_index.h): the tiles of its hot pass in front of each item,
      * the tile sums of its two scans over the items and the word that holds all blocks; ONE allocation, made by the plan's
      * first such call and grown by a later one of more items or tiles */
